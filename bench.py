@@ -2,6 +2,15 @@
 """Benchmark of the MI355X multi-view epipolar matcher (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c2cube|c2match]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs when ``--dump-outputs DIR`` is given and prints the result line.
+Everything else described below that is measured or checked after the timed
+region (the comparisons with the CPU oracle, the CPU baselines, the
+PCIe-inclusive launch, the kernel timed alone, the HBM write probe, the clock
+samples, the N > 1 step split and the nested c2match line) runs only with
+``--full``.
 
 A *step* is one pass of the hot path over this rank's whole batch of
 synthetic scenes (resident in HBM): pairwise symmetric epipolar residuals for
@@ -28,25 +37,35 @@ calls).
 
 ``python bench.py --gpus N`` (N > 1) run without a launcher starts the N
 ranks itself: torchrun in a child process, this process making no GPU call;
-every rank checks that the process group it joined has N ranks.  After the
-timed region every association row of the last step -- all ranks' rows, as
-gathered to rank 0 -- is compared with the CPU oracle (``parity_rows``).
+every rank checks that the process group it joined has N ranks.  With
+``--full``, after the timed region every association row of the last step --
+all ranks' rows, as gathered to rank 0 -- is compared with the CPU oracle
+(``parity_rows``).
 By default every launch of the timed steps writes its own output allocation
 as far as HBM holds them (C3: five launches of 2,000 scenes into five 50 GB
 buffers, 253 GB, one per launch of a step; C2: one per step), taken round
 robin, so a step's outputs all stay resident and the measurement covers much
 of the HBM rather than wherever one launch-sized buffer happened to land (the
 same launch runs up to ~20% apart on different allocations: DESIGN.md §5);
-``--output ring`` reuses one buffer.  The first scene of the launch each
-allocation last held is compared with the oracle bit for bit (``parity``).
+``--output ring`` reuses one buffer.  With ``--full`` the first scene of the
+launch each allocation last held is compared with the oracle bit for bit
+(``parity``).
 
 ``--workload c2match`` times what ``match_objects`` returns at C2 scale (cube +
 scipy-identical assignment + threshold/sort/DLT, units = captures).
 
+``--dump-outputs DIR`` saves what the last timed step returned to its caller
+as float32 / float64 ``DIR/<name>.npy`` (``dump_save`` below), at most 64 MB
+in all: with the same arguments the inputs, and the elements sampled from
+outputs too large to save whole, are the same from run to run.  With N > 1
+the residual matrices or cubes (and every c2match file) are rank 0's launches
+only; the association rows are all ranks', as gathered to rank 0.
+
 Printed by rank 0: ONE JSON line with value = total pairs/s over all ranks,
-the dominant kernel's roofline (achieved algorithmic GB/s from HIP events on
-the launch stream vs the 8 TB/s HBM peak) and a CPU baseline (the C/OpenMP
-restatement in oracle/, timed on a bounded sample on this host).
+``ms_per_step`` and the dominant kernel's roofline (achieved algorithmic GB/s
+from HIP events on the launch stream vs the 8 TB/s HBM peak); with ``--full``
+also a CPU baseline (the C/OpenMP restatement in oracle/, timed on a bounded
+sample on this host).
 """
 from __future__ import annotations
 
@@ -373,6 +392,61 @@ class ClockSampler:
                 "max_mhz": float(s.max())}
 
 
+class NoClocks:
+    """Stands in for ClockSampler in a plain run: no thread, no samples."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+    def temperatures(self):
+        return None
+
+    def summary(self, kind: str = "sclk"):
+        return None
+
+
+def _sample(rng, n: int, k: int) -> np.ndarray:
+    """Sorted indices into an output of n elements: all of them when n <= k,
+    else k drawn (with repeats) by ``rng``."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(rng.integers(0, n, size=k, dtype=np.int64))
+
+
+DUMP_SEED = 20240607            # of the element samples --dump-outputs takes
+DUMP_BUDGET = 60 << 20          # bytes of all the files' data (the limit is 64 MB)
+
+
+def dump_save(out_dir: str, arrays: dict) -> dict:
+    """Save {name: array} as out_dir/<name>.npy (float32 stays, everything
+    else becomes float64) -> {name: [elements, dtype]} for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    info, total = {}, 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = [int(a.size), str(a.dtype)]
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    return info
+
+
+def pairwise_dump_positions(plan, idx: np.ndarray) -> np.ndarray:
+    """Positions inside a PairwisePlan's (possibly pitched) residual output of
+    the elements ``idx`` of its unpitched layout (what plan.compact() returns)."""
+    if plan.dist_size == plan.n_dist:
+        return idx
+    offs = np.zeros(plan.na.size + 1, np.int64)
+    np.cumsum(plan.na * plan.nb, out=offs[1:])
+    sp = np.searchsorted(offs, idx, side="right") - 1
+    r = idx - offs[sp]
+    nb = plan.nb[sp]
+    return plan.dist_offs_host[sp] + r // nb * plan.ld[sp] + r % nb
+
+
 def output_slots(n_launch: int, slot_bytes: int, free_bytes: int,
                  reserve_bytes: int = 8 << 30) -> int:
     """Output allocations for a step: one per launch when HBM holds them with
@@ -529,7 +603,8 @@ def run_match(args, env, wl, kernel_options):
     line, ok = match_line(args, env, wl, kernel_options, steps=args.steps, warmup=args.warmup,
                           cube_mode=args.cube, cpu_seconds=args.cpu_seconds,
                           n_chunks_req=args.match_chunks, lsap_input=args.lsap_input,
-                          pipeline=args.match_pipeline == "on")
+                          pipeline=args.match_pipeline == "on", full=args.full,
+                          dump_dir=args.dump_outputs)
     if line is None:
         return
     print(json.dumps(line), flush=True)
@@ -542,7 +617,7 @@ FREE_LSAP_INPUT = "blocks"     # the cube-free chain's default block source (--l
 
 
 def match_line(args, env, wl, kernel_options, *, steps, warmup, cube_mode="free", cpu_seconds=0.0,
-               n_chunks_req=1, lsap_input="auto", pipeline=False):
+               n_chunks_req=1, lsap_input="auto", pipeline=False, full=False, dump_dir=None):
     """What ``match_objects`` returns, at C2 scale (the ``c2match`` workload).
 
     A step is every scene of this rank through the device chain of
@@ -694,7 +769,7 @@ def match_line(args, env, wl, kernel_options, *, steps, warmup, cube_mode="free"
            for _ in range(steps)]
     env.barrier()
     torch.cuda.synchronize(dev)
-    with ClockSampler(dev) as clocks:
+    with (ClockSampler(dev) if full else NoClocks()) as clocks:
         t_start = time.perf_counter()
         for s_ in range(steps):
             outs = step(evs[s_], chunks=sets[s_ % len(sets)])
@@ -717,7 +792,36 @@ def match_line(args, env, wl, kernel_options, *, steps, warmup, cube_mode="free"
 
     # ---- parity (untimed): a few scenes against the CPU chain --------------
     parity_ok, detail = bool((status == 0).all()), []
-    if env.is_root:
+    # ---- --dump-outputs: what the last step's chain returned on rank 0 (its
+    # own scenes only when N > 1), scene by scene in the plans' layout (entries no scene owns, and match rows past a
+    # scene's count, are zero) --------------------------------------------------
+    dumped = None
+    if dump_dir and env.is_root:
+        cols = {k: [] for k in ("row_ind", "col_ind", "status", "match", "cost", "X", "count")}
+        for ch, (r, c, st, match, cost, X, count) in zip(chunks, outs):
+            lp = ch["lplan"]
+            k_h = count.cpu().numpy().astype(np.int64)
+            lo = lp.out_offs_host[:-1]
+            pos = np.arange(lp.n_out)
+            own = np.searchsorted(lp.out_offs_host, pos, side="right") - 1
+            within = pos - lo[own]
+            assigned = within < np.minimum(lp.rows, lp.cols)[own]
+            matched = within < k_h[own]
+            for key, t, keep in (("row_ind", r, assigned), ("col_ind", c, assigned),
+                                 ("match", match, matched), ("cost", cost, matched), ("X", X, matched)):
+                a = t[:lp.n_out].cpu().numpy().astype(np.float32 if key == "cost" else np.float64)
+                a[~keep] = 0
+                cols[key].append(a)
+            cols["status"].append(st.cpu().numpy())
+            cols["count"].append(k_h)
+        cols = {k: np.concatenate(v) for k, v in cols.items()}
+        # 68 bytes per assignment entry, 16 per scene: a seeded sample of more than fit
+        rng = np.random.default_rng(DUMP_SEED)
+        e_idx = _sample(rng, len(cols["cost"]), DUMP_BUDGET // 2 // 68)
+        s_idx = _sample(rng, len(cols["count"]), DUMP_BUDGET // 2 // 16)
+        dumped = dump_save(dump_dir, {k: v[s_idx if k in ("status", "count") else e_idx]
+                                      for k, v in cols.items()})
+    if full and env.is_root:
         from oracle import oracle as O
         picks = sorted({0, n_local // 3, (2 * n_local) // 3, n_local - 1})
         for s in picks:
@@ -812,7 +916,7 @@ def match_line(args, env, wl, kernel_options, *, steps, warmup, cube_mode="free"
     d_ms, d_bytes, d_kernel = stages[dom]
     achieved = d_bytes / (d_ms * 1e-3) / 1e9 if d_ms > 0 else None
     cpu = None
-    if cpu_seconds > 0:
+    if full and cpu_seconds > 0:
         threads, threads_src = host_cpu_threads()
         match_cpu_chain(batch, proj, 0, threshold, nthreads=threads)      # warm
         n_cpu, t0 = 0, time.perf_counter()
@@ -882,7 +986,10 @@ def match_line(args, env, wl, kernel_options, *, steps, warmup, cube_mode="free"
                               "(lsap.streamed_gb)")},
         "valu_roofline": valu,
         "cpu_baseline": cpu,
-        "parity": f"{'equal' if parity_ok else 'MISMATCH'} vs the CPU chain on {len(detail)} scenes",
+        "full": bool(full),
+        "outputs_dumped": dumped,
+        "parity": (f"{'equal' if parity_ok else 'MISMATCH'} vs the CPU chain on {len(detail)} scenes"
+                   if full else "skipped" if parity_ok else "an assignment's status is not 0"),
         "parity_detail": detail,
     }
     return line, parity_ok
@@ -907,8 +1014,21 @@ def main():
     ap.add_argument("--dump-association", default=None, metavar="DIR",
                     help="rank 0 saves the gathered association rows (argmin.npy, minval.npy, "
                          "in global scene order) after the timed region")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned (the residual matrices "
+                         "or cubes of rank 0's launches, all ranks' argmin and min rows as "
+                         "gathered; c2match: rank 0's assignment, matches, costs, points) as "
+                         "float32 / float64 DIR/<name>.npy, at most 64 MB in all: a fixed seeded "
+                         "sample of an output too large to save whole")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: "
+                         "the comparisons with the CPU oracle (parity, parity_rows), the CPU "
+                         "baselines, the PCIe-inclusive launch, the kernel timed alone, the HBM "
+                         "write probe, the clock and temperature samples, the N > 1 step split "
+                         "and (c3 on one GPU) the nested c2match line; the options below that "
+                         "choose among these apply only with --full")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target length of the CPU-baseline sample (0 disables)")
+                    help="--full: target length of the CPU-baseline sample (0 disables)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--output", choices=["resident", "ring"], default="resident",
                     help="resident (default): one output allocation per launch of the timed "
@@ -922,7 +1042,7 @@ def main():
                          "holding all K steps (one GPU only: a step with N > 1 has collectives); "
                          "off: eager op calls")
     ap.add_argument("--parity", choices=["full", "scene"], default="full",
-                    help="full (default): after timing, every association row of the last step "
+                    help="--full only.  full (default): after timing, every association row of the last step "
                          "(all ranks' rows, as gathered to rank 0) against the oracle, which each "
                          "rank computes for its own scenes and sends to rank 0 over a gloo group; "
                          "scene: only the last launch's first scene")
@@ -943,8 +1063,8 @@ def main():
                          "pass's fp64 pair residuals, no cube is written; keep: the cost cubes are "
                          "written and read")
     ap.add_argument("--c2match", choices=["auto", "off"], default="auto",
-                    help="auto (default): the c3 workload on one GPU also measures c2match "
-                         "(cube-free) after its own line's parity and nests it in the line as "
+                    help="--full only.  auto (default): the c3 workload on one GPU also measures "
+                         "c2match (cube-free) after its own line's parity and nests it in the line as "
                          "\"c2match\"; off: not")
     ap.add_argument("--lsap-input", choices=["auto", "bmin8", "blocks", "cost"], default="auto",
                     help="c2match: the assignment's candidate blocks refined by the 8-row minima "
@@ -1207,7 +1327,7 @@ def main():
     torch.cuda.synchronize(dev)
     env.barrier()
     window_start = dispatched[0]
-    with ClockSampler(dev) as clocks:
+    with (ClockSampler(dev) if args.full else NoClocks()) as clocks:
         t_start = time.perf_counter()
         if step_graph is not None:   # one event pair over the timed region: no markers between steps
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1231,12 +1351,42 @@ def main():
     elapsed = max_over_ranks(env, elapsed)
     ms_per_step = elapsed / args.steps * 1e3
 
+    # ---- --dump-outputs: what the last timed step returned (untimed) --------
+    # the residual matrices (or cubes) of rank 0's launches in launch order, in
+    # the unpitched layout, and the association rows in scene order (all ranks'
+    # rows as gathered to rank 0): whole when they fit, else the elements a
+    # seeded generator names -- the same ones in every run with these arguments
+    dumped = None
+    if args.dump_outputs and env.is_root:
+        rng = np.random.default_rng(DUMP_SEED)
+        per = DUMP_BUDGET // 16          # elements per array: two float32, one float64
+        name = "dist" if wl["mode"] == "pairwise" else "cube"
+        parts = []
+        for k, c in enumerate(chunks):
+            slot = graph_slot[(args.steps - 1, k)] if graphs is not None else last_slot[id(c)]
+            if slot_owner.get(slot) != k:
+                # a later launch of the step reused this launch's allocation
+                # (fewer allocations than launches): the same launch once more
+                launch(c)
+                slot = last_slot[id(c)]
+            idx = _sample(rng, c.units, max(1, per // len(chunks)))
+            pos = pairwise_dump_positions(c.plan, idx) if wl["mode"] == "pairwise" else idx
+            parts.append(out_slots[slot][:c.size][torch.from_numpy(pos).to(dev)].cpu().numpy())
+        if env.initialised:
+            d_am, d_mv = (g.reshape(-1) for g in gathered[:2])
+        else:
+            d_am, d_mv = argmin, minval
+        ridx = torch.from_numpy(_sample(rng, int(d_am.numel()), per)).to(d_am.device)
+        dumped = dump_save(args.dump_outputs, {
+            name: np.concatenate(parts),
+            "argmin": d_am[ridx].cpu().numpy(), "minval": d_mv[ridx].cpu().numpy()})
+
     # ---- N > 1: the step's two parts timed apart (untimed for `value`) -----
     # compute alone (every launch, no collective) and the association gather
     # alone, each bracketed by barrier + sync and maxed over ranks; and the
     # exposed tail of the timed steps: last launch done -> gather done
     split = None
-    if env.initialised:
+    if args.full and env.initialised:
         reps = max(1, min(args.steps, 5))
         torch.cuda.synchronize(dev)
         env.barrier()
@@ -1302,7 +1452,7 @@ def main():
     # transport under test); rank 0 compares them with every row it holds
     # after the step's gather: rank 0's own rows and what ranks 1..N-1 sent.
     parity_rows, parity_detail = None, None
-    if args.parity == "full":
+    if args.full and args.parity == "full":
         from oracle import oracle as O
         t0 = time.perf_counter()
         nth = cpu_threads()
@@ -1348,7 +1498,7 @@ def main():
     # launch whose output each allocation still holds, so every allocation the
     # last step wrote is checked (C3: five scenes, five 50 GB allocations) ----
     parity, parity_ok = "skipped", True
-    if env.is_root:
+    if args.full and env.is_root:
         from oracle import oracle as O
         C, P = batch.n_cams, batch.n_pairs
         n_units, checked = 0, []
@@ -1390,7 +1540,7 @@ def main():
     # the same launch fed from pinned host buffers: H2D of centroids, offsets
     # and F, the kernel, D2H of the association rows; distances stay in HBM
     pcie = None
-    if env.is_root:
+    if args.full and env.is_root:
         c = chunks[-1]
         srcs = [t.cpu().pin_memory() for t in (c.pts, c.cam_offs, c.F)]
         am = argmin[c.row_base:c.row_base + c.plan.n_rows]
@@ -1421,7 +1571,7 @@ def main():
     # (HIP events around each, the stream drained between them), next to the
     # timed period, which overlaps launch tails (steps / steps2 graphs) ------
     kernel_iso = None
-    if env.is_root:
+    if args.full and env.is_root:
         iso = []
         for _ in range(5):
             i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1443,7 +1593,7 @@ def main():
     # ---- achievable HBM write bandwidth on this box (same store form), over
     # the same output allocations the launches wrote ----------------------------
     probe_gbs = probe2_gbs = None
-    if env.is_root:
+    if args.full and env.is_root:
         pe0, pe1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for buf in out_slots:
             ops.hbm_write_probe(buf)
@@ -1498,7 +1648,7 @@ def main():
     # the CPU baseline runs at every N, on rank 0 after the timed region (the
     # other ranks are done by then), on a sample of rank 0's own scenes
     cpu = None
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         cpu = cpu_baseline(batch, wl["mode"], args.cpu_seconds)
         if world > 1:
             cpu["note"] = (f"rank 0 of {world}, after the timed region, on a sample of its own "
@@ -1588,6 +1738,8 @@ def main():
                                 "after": dispatched[0] - window_start - window_timed,
                                 "slots": n_slots, "launches_per_step": len(chunks)},
         },
+        "full": bool(args.full),
+        "outputs_dumped": dumped,
         "cpu_baseline": cpu,
         "pcie_inclusive": pcie,
         "parity": parity,
@@ -1603,7 +1755,7 @@ def main():
     # of match_captures) after the C3 line's own parity, with its own parity
     # against the CPU chain, nested in this line ----------
     nested_ok = True
-    if args.workload == "c3" and world == 1 and args.c2match == "auto":
+    if args.full and args.workload == "c3" and world == 1 and args.c2match == "auto":
         out_slots.clear()                 # C3's 253 GB of output allocations
         chunks.clear()
         graphs = step_graph = gatherer = None
@@ -1613,7 +1765,7 @@ def main():
         t0 = time.perf_counter()
         nested, nested_ok = match_line(args, env, dict(WORKLOADS["c2match"]), None, steps=20, warmup=3,
                                        cube_mode="free", cpu_seconds=min(args.cpu_seconds, 5.0),
-                                       pipeline=args.match_pipeline == "on")
+                                       pipeline=args.match_pipeline == "on", full=True)
         nested["wall_s"] = time.perf_counter() - t0
         nested["note"] = ("BASELINE configs[1]'s association (C2: 1,000 captures x 3 x 256, what "
                           "match_objects returns), run after this line's timed region on the same "

@@ -102,7 +102,8 @@ def test_bench_rccl_process_group_single_rank(tmp_path):
                MASTER_PORT=str(_free_port()))
     env.pop("MVM_DIST_BACKEND", None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--scenes", "40",
-                        "--chunk", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0"],
+                        "--chunk", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -138,7 +139,7 @@ def test_ranks_real_kernel_equal_single_process(tmp_path, world, n_scenes):
     from oracle import oracle as O
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--workload", "c3", "--scenes", str(n_scenes), "--chunk", "8", "--steps", "1",
-              "--warmup", "1", "--cpu-seconds", "0"]
+              "--warmup", "1", "--cpu-seconds", "0", "--full"]
     env1 = dict(os.environ)
     for k in ("MVM_DIST_FORCE", "MVM_DIST_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env1.pop(k, None)
@@ -209,7 +210,7 @@ def test_bench_graph_replay_single_gpu(tmp_path, workload, mode):
     mode, steps = (mode.split("-")[0], int(mode.split("-")[1])) if "-" in mode else (mode, 2)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", workload,
                         "--scenes", "24", "--chunk", "8", "--steps", str(steps), "--warmup", "1",
-                        "--cpu-seconds", "0", "--graph", mode],
+                        "--cpu-seconds", "0", "--graph", mode, "--full"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -300,7 +301,7 @@ def test_bench_gpus_n_without_launcher(tmp_path, world):
     n_scenes = 24
     line = _run_bench(repo, [sys.executable, "bench.py", "--gpus", str(world), "--scenes",
                              str(n_scenes), "--chunk", "8", "--steps", "1", "--warmup", "1",
-                             "--cpu-seconds", "0"], env, tmp_path, "nolauncher")
+                             "--cpu-seconds", "0", "--full"], env, tmp_path, "nolauncher")
     assert line["n_gpus"] == world
     assert line["process_group"]["world_size"] == world
     rows = n_scenes * 6 * 1024
@@ -324,7 +325,7 @@ def test_bench_c2match_line_small(cube, extra):
     env.pop("MVM_DIST_FORCE", None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "c2match",
                         "--scenes", "24", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0",
-                        "--cube", cube, *extra],
+                        "--cube", cube, "--full", *extra],
                        env=env, capture_output=True, text=True, timeout=300, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -332,3 +333,82 @@ def test_bench_c2match_line_small(cube, extra):
     assert all(all(v for k, v in d.items() if k != "scene" and k != "matches")
                for d in line["parity_detail"]), line["parity_detail"]
     assert line["value"] > 0 and line["config"]["n_scenes_total"] == 24
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["c2", "c2-ring", "c2cube", "c2match"])
+def test_bench_plain_run_dumps_last_step(tmp_path, workload):
+    """A plain `bench.py --dump-outputs DIR` (no --full): the line holds the
+    headline fields and none of the --full legs, and the files hold what the
+    last timed step returned, compared with the CPU oracle: every element
+    where the output is saved whole (c2: three steps of the two-stream graph,
+    the last one's rows on the first stream; c2match), the seeded sample of
+    the c2cube cubes; two launches per step.  c2-ring: both launches write one
+    output allocation (--output ring), so the first launch's matrices are
+    gone when the step ends and the dump runs that launch once more."""
+    import json
+    import subprocess
+    import sys
+    from bpc_baseline_amd.synth import make_scenes
+    from oracle import oracle as O
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n_scenes = 6
+    out = tmp_path / "dump"
+    workload, *ring = workload.split("-")
+    extra = ["--output", "ring"] if ring else []
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", workload,
+                        "--scenes", str(n_scenes), "--chunk", "4", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out), *extra],
+                       env=_bench_env(), capture_output=True, text=True, timeout=300, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["unit"]
+    assert line["full"] is False and line["cpu_baseline"] is None
+    assert line["parity"] == "skipped" and "c2match" not in line
+    if ring:
+        assert line["config"]["output_allocations"] == 1 and line["config"]["launches_per_step"] == 2
+    files = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+    assert set(files) == set(line["outputs_dumped"])
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    b = make_scenes(n_scenes, 3, 256, seed=0)
+    if workload == "c2match":
+        # the CPU chain bench.py --full checks four scenes against, on every scene
+        import bench
+        from bpc_baseline_amd.inference.utils.camera_utils import projection_matrices
+        proj = projection_matrices(b.meta["Ks"], b.meta["RTs"])
+        assert (files["status"] == 0).all()
+        for s in range(n_scenes):
+            cube, rr, rc, ref, rX = bench.match_cpu_chain(b, proj, s, 30.0)
+            cube = cube.reshape(np.diff(b.cam_offs[3 * s:3 * s + 4]))
+            lo = 256 * s                  # min(N * M, P) assignment entries per scene
+            assert rr.size == 256
+            assert np.array_equal(files["row_ind"][lo:lo + 256], rr)
+            assert np.array_equal(files["col_ind"][lo:lo + 256], rc)
+            k = int(files["count"][s])
+            assert k == len(ref) and k > 0
+            assert np.array_equal(files["match"][lo:lo + k], np.asarray(ref).reshape(-1, 3))
+            assert np.array_equal(files["cost"][lo:lo + k], np.array([cube[m] for m in ref], np.float32))
+            # the DLT's bound in bench.py's own parity (fp64 SVD against the GPU's solve)
+            assert np.allclose(files["X"][lo:lo + k], rX, rtol=1e-10, atol=1e-9)
+            assert not files["match"][lo + k:lo + 256].any() and not files["X"][lo + k:lo + 256].any()
+        return
+    if workload == "c2":
+        rd, ra, rm, _, _ = O.pairwise(b.pts, b.cam_offs, b.F, b.pairs, n_scenes, 3)
+        got = files["dist"]
+    else:
+        # 6 x 256^3 triples are more than the files may hold: the elements the
+        # seeded generator names, launch by launch (two launches of 3 scenes)
+        import bench
+        rd, ra, rm, _, _ = O.cube(b.pts, b.cam_offs, b.F, n_scenes)
+        rng = np.random.default_rng(bench.DUMP_SEED)
+        per = bench.DUMP_BUDGET // 16 // 2
+        half = rd.size // 2
+        assert half > per
+        rd = np.concatenate([rd.reshape(-1)[k * half:(k + 1) * half][bench._sample(rng, half, per)]
+                             for k in range(2)])
+        got = files["cube"]
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.int32), rd.reshape(-1).view(np.int32))
+    assert np.array_equal(files["argmin"], ra)
+    assert np.array_equal(files["minval"].view(np.int32), rm.view(np.int32))

@@ -611,3 +611,24 @@ def test_capture_stream_abandoned_then_reused(monkeypatch):
     pool, procs = seen[0]
     assert pool is not bm.rig_worker_pool(2)
     assert not pool.procs and all(pr.poll() is not None for pr in procs)
+
+
+def test_bench_dump_sample_positions():
+    """--dump-outputs samples the residuals in the unpitched layout: the
+    positions it reads inside a pitched output are those of plan.compact(),
+    and the sample is the same for the same seed (whole when it fits)."""
+    import bench
+    from bpc_baseline_amd import ops
+    counts = np.array([[5, 33, 7], [40, 1, 64]])
+    cam_offs = np.concatenate([[0], np.cumsum(counts.reshape(-1))])
+    pairs = [(0, 1), (0, 2), (1, 2)]
+    for align in (1, "auto"):
+        plan = ops.PairwisePlan(cam_offs, 2, 3, pairs, device="cpu", row_align=align)
+        assert (plan.dist_size > plan.n_dist) == (align == "auto")
+        dist = torch.arange(plan.dist_size, dtype=torch.float32)
+        idx = bench._sample(np.random.default_rng(bench.DUMP_SEED), plan.n_dist, 500)
+        again = bench._sample(np.random.default_rng(bench.DUMP_SEED), plan.n_dist, 500)
+        assert np.array_equal(idx, again) and idx.size == 500 and (np.diff(idx) >= 0).all()
+        pos = bench.pairwise_dump_positions(plan, idx)
+        assert np.array_equal(dist.numpy()[pos], plan.compact(dist).numpy()[idx])
+    assert np.array_equal(bench._sample(np.random.default_rng(1), 9, 9), np.arange(9))

@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
   for a in "$@"; do
     i=$((i+1))
     x=(); [ "$a" != "default" ] && x=($a)
-    timeout -k 10 300 python bench.py --workload $W --steps 10 --warmup 3 --cpu-seconds 0 --parity scene "${x[@]}" > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err || { tail -5 $O/v${i}_r$r.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --workload $W --steps 10 --warmup 3 --cpu-seconds 0 --parity scene "${x[@]}" > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err || { tail -5 $O/v${i}_r$r.err; exit 1; }
     echo "[$a] $(python tools/summarise_line.py $O/v${i}_r$r.json | cut -c1-150)"
   done
 done

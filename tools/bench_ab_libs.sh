@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
   for lib in "$@"; do
     i=$((i+1))
     if [ "$lib" = "default" ]; then unset MVM_LIB_PATH; else export MVM_LIB_PATH=$lib; fi
-    timeout -k 10 300 python bench.py --workload $W --steps 10 --warmup 3 --cpu-seconds 0 --parity scene > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err || { tail -5 $O/v${i}_r$r.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --workload $W --steps 10 --warmup 3 --cpu-seconds 0 --parity scene > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err || { tail -5 $O/v${i}_r$r.err; exit 1; }
     echo "[$(basename $lib)] $(python tools/summarise_line.py $O/v${i}_r$r.json | cut -c1-150)"
   done
 done

@@ -55,13 +55,13 @@ check)
   rc=$?; tail -22 "$O/pytest_gpu.log"; exit $rc ;;
 bench)
   W=$1; shift
-  timeout -k 10 "$LIMIT" python bench.py --workload "$W" "$@" > "$O/bench_$W.json" \
+  timeout -k 10 "$LIMIT" python bench.py --full --workload "$W" "$@" > "$O/bench_$W.json" \
     2> "$O/bench_$W.err" || fail "bench $W" "$O/bench_$W.err"
   python tools/summarise_line.py "$O/bench_$W.json" ;;
 trace)
   W=$1; shift
   timeout -k 10 "$LIMIT" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_$W" \
-    -o run -- python bench.py --workload "$W" "$@" > "$O/bench_$W.json" 2> "$O/trace_$W.err" \
+    -o run -- python bench.py --full --workload "$W" "$@" > "$O/bench_$W.json" 2> "$O/trace_$W.err" \
     || fail "trace $W" "$O/trace_$W.err"
   python tools/summarise_line.py "$O/bench_$W.json" &&
   python tools/profile_window.py "$O/bench_$W.json" "$O/trace_$W/run_kernel_trace.csv" \
@@ -70,7 +70,7 @@ pmc)
   W=$1; shift
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $C --output-format csv -d "$O/pmc_${C}_$W" -o run -- \
-      python bench.py --workload "$W" --steps 1 --warmup 0 --cpu-seconds 0 --c2match off "$@" \
+      python bench.py --full --workload "$W" --steps 1 --warmup 0 --cpu-seconds 0 --c2match off "$@" \
       > "$O/pmc_${C}_$W.log" 2>&1 || fail "pmc $C $W" "$O/pmc_${C}_$W.log"
   done
   echo "pmc $W ok" ;;
@@ -111,11 +111,11 @@ slots)
   done
   echo slots ok ;;
 match)
-  timeout -k 10 "$LIMIT" python -u bench.py --workload c2match "$@" > "$O/bench_c2match.json" \
+  timeout -k 10 "$LIMIT" python -u bench.py --full --workload c2match "$@" > "$O/bench_c2match.json" \
     2> "$O/bench_c2match.err" || fail "bench c2match" "$O/bench_c2match.err"
   # last: the profiler's teardown has crashed after writing its files
   timeout -k 10 "$LIMIT" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_c2match" \
-    -o run -- python -u bench.py --workload c2match --cpu-seconds 0 "$@" > "$O/trace_c2match.json" \
+    -o run -- python -u bench.py --full --workload c2match --cpu-seconds 0 "$@" > "$O/trace_c2match.json" \
     2> "$O/trace_c2match.err"
   rc=$?; echo "match trace rc=$rc (run it last: nothing after a crashed process)"; exit $rc ;;
 cubeab)
@@ -157,12 +157,12 @@ cubefree)
     > "$O/pytest_cubefree.log" 2>&1 || fail "cube-free suites" "$O/pytest_cubefree.log"
   tail -1 "$O/pytest_cubefree.log"
   for M in free keep free keep; do
-    timeout -k 10 "$LIMIT" python -u bench.py --workload c2match --cube $M --cpu-seconds 0 "$@" \
+    timeout -k 10 "$LIMIT" python -u bench.py --full --workload c2match --cube $M --cpu-seconds 0 "$@" \
       >> "$O/bench_c2match_$M.json" 2>> "$O/bench_c2match_$M.err" || fail "c2match $M" "$O/bench_c2match_$M.err"
     python tools/summarise_line.py <(tail -1 "$O/bench_c2match_$M.json")
   done
   timeout -k 10 "$LIMIT" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_c2match_free" \
-    -o run -- python -u bench.py --workload c2match --cube free --cpu-seconds 0 "$@" \
+    -o run -- python -u bench.py --full --workload c2match --cube free --cpu-seconds 0 "$@" \
     > "$O/trace_c2match_free.json" 2> "$O/trace_c2match_free.err"
   rc=$?; echo "cubefree trace rc=$rc"; exit $rc ;;
 cfab)
@@ -174,19 +174,19 @@ cfab)
   for rnd in 1 2; do
     for V in ${CF_VARIANTS:-default cube_tile_rows=32}; do
       OPT=""; [ "$V" != default ] && OPT="--options $V"
-      timeout -k 10 "$LIMIT" python -u bench.py --workload c2match --cube free --cpu-seconds 0 $OPT "$@" \
+      timeout -k 10 "$LIMIT" python -u bench.py --full --workload c2match --cube free --cpu-seconds 0 $OPT "$@" \
         > "$O/cf_${V}_$rnd.json" 2> "$O/cf_${V}_$rnd.err" || fail "c2match $V" "$O/cf_${V}_$rnd.err"
       echo "== $V round $rnd"; python tools/summarise_line.py "$O/cf_${V}_$rnd.json" | tail -1
     done
   done
   for C in ${CF_CHUNKS:-2 4}; do
-    timeout -k 10 "$LIMIT" python -u bench.py --workload c2match --cube free --cpu-seconds 0 --match-chunks $C "$@" \
+    timeout -k 10 "$LIMIT" python -u bench.py --full --workload c2match --cube free --cpu-seconds 0 --match-chunks $C "$@" \
       > "$O/cf_chunks$C.json" 2> "$O/cf_chunks$C.err" || fail "c2match chunks $C" "$O/cf_chunks$C.err"
     echo "== $C chunks"; python tools/summarise_line.py "$O/cf_chunks$C.json"
   done
   timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY \
     SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_LDS --output-format csv -d "$O/sq_cf" -o run -- \
-    python bench.py --workload c2match --cube free --steps 2 --warmup 1 --cpu-seconds 0 > "$O/sq_cf.log" 2>&1 \
+    python bench.py --full --workload c2match --cube free --steps 2 --warmup 1 --cpu-seconds 0 > "$O/sq_cf.log" 2>&1 \
     || fail "sq c2match" "$O/sq_cf.log"
   for K in triplet_minima sp_solve sp_lists sp_bmin8_reduce; do
     python tools/summarise_sq.py "$O/sq_cf/run_counter_collection.csv" $K 16777216000 --what "c2match free $K" \
