@@ -67,6 +67,45 @@ int mvm_resolve_options(const mvm_options *in, mvm_options &out) {
     return MVM_OK;
 }
 
+int mvm_raise_dynamic_lds(const void *kernel, size_t bytes) {
+    if (bytes > 64 * 1024 &&
+        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", bytes);
+    return MVM_OK;
+}
+
+int mvm_resolve_limit(int32_t opt, int dflt, int cap) {
+    const int v = opt == 0 ? dflt : opt;
+    return v < 0 ? 0 : (v > cap ? cap : v);
+}
+
+int64_t mvm_coresident_blocks(const void *kernel, int threads, size_t lds) {
+    int occ = 0, cus = 0, dev = 0;
+    const bool ok = hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) == hipSuccess;
+    return ok ? (int64_t)cus * occ : 0;
+}
+
+int64_t mvm_lsap_plan_offsets(const char *who, int32_t n, const int64_t *rows, const int64_t *cols,
+                              size_t elem, int64_t (*need)(int64_t nr, int64_t nc, bool tr, size_t elem),
+                              int64_t *ws_offs, int64_t *out_offs) {
+    int64_t w = 0, o = 0;
+    for (int32_t p = 0; p < n; ++p) {
+        if (rows[p] < 0 || cols[p] < 0 || rows[p] > 0x7FFFFFFF || cols[p] > 0x7FFFFFFF)
+            return mvm_fail(-1, "%s: problem dimensions out of range", who);
+        ws_offs[p] = w;
+        out_offs[p] = o;
+        const bool tr = cols[p] < rows[p];
+        const int64_t nr = tr ? cols[p] : rows[p], nc = tr ? rows[p] : cols[p];
+        if (nr) w += need(nr, nc, tr, elem);
+        o += nr;
+    }
+    ws_offs[n] = w;
+    out_offs[n] = o;
+    return w;
+}
+
 extern "C" {
 
 // tools/build_variant.py names its A/B builds (some compute wrong results by design)

@@ -2079,10 +2079,8 @@ int cube_launch(const double *pts_dev, const int64_t *cam_offs_dev, const double
         c.ib = max_n <= 32 ? max_n : 16;
         c.i_blocks = (max_n + c.ib - 1) / c.ib;
         const size_t lds = small_lds_bytes(max_n, c.ib);
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&triplet_small_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
+        if ((st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(&triplet_small_kernel), lds)))
+            return st;
         const int64_t blocks = (int64_t)n_scenes * c.i_blocks;
         if ((st = grid_check(blocks))) return st;
         triplet_small_kernel<<<dim3((unsigned)blocks), dim3(kThreads), lds, s>>>(c);

@@ -1,7 +1,8 @@
 // mvm_device.h — device-side building blocks shared by the matcher's kernels
 // (mvm_pairwise.hip, mvm_cube.hip): the reference's line / distance
-// arithmetic, the np.argmin ordering keys and wave reductions, and the
-// store forms.  Internal to the library (not part of the C ABI).
+// arithmetic, the np.argmin ordering keys and their reductions (over
+// mvm_wave.h), and the store forms.  Internal to the library (not part of
+// the C ABI).
 //
 // Arithmetic is float64 and reproduces the reference bit for bit: FMAs are
 // placed exactly where numpy/OpenBLAS placed them in the reference run
@@ -14,6 +15,8 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+
+#include "mvm_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -96,32 +99,6 @@ __device__ __forceinline__ uint32_t key_of(float v) {
 
 __device__ __forceinline__ float value_of_key(uint32_t k) {
     return (k == 0u || k == kKeyInvalid) ? __uint_as_float(0x7FC00000u) : __uint_as_float(k - 1u);
-}
-
-// DPP min step: v = min(v, v from the lane DPP control CTRL selects).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_min(uint32_t v) {
-    // old = UINT_MAX (umin's identity) lets the DPP-combine pass fold the move
-    // into the min (one v_min_u32_dpp per step)
-    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, 0xF, 0xF, false);
-    return o < v ? o : v;
-}
-
-// Minimum over the wave, returned as a uniform (SGPR) value: four DPP steps
-// reduce each 16-lane row in registers (quad_perm [1,0,3,2], quad_perm
-// [2,3,0,1], row_half_mirror, row_mirror), then the four row minima are read
-// with v_readlane and combined on the scalar unit.  No LDS round trips.
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    v = dpp_min<0xB1>(v);
-    v = dpp_min<0x4E>(v);
-    v = dpp_min<0x141>(v);
-    v = dpp_min<0x140>(v);
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
-    const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
 }
 
 // Reduce (key, idx) over the wave: minimum key, then the lowest column index
@@ -230,12 +207,6 @@ __device__ __forceinline__ uint32_t lane_group_min(uint32_t v) {
         v = o < v ? o : v;
     }
     return v;
-}
-
-// The partner lane's value under DPP control CTRL (every lane has a partner).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_from(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, 0xF, 0xF, false);
 }
 
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }

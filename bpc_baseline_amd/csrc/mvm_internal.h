@@ -4,6 +4,8 @@
 #pragma once
 
 #include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
 
 #include "mvmatch.h"
 
@@ -13,3 +15,15 @@ void mvm_clear_error();
 int mvm_check_launch(const char *what);
 // *in (NULL = defaults) -> out, every field present; MVM_OK or an error code
 int mvm_resolve_options(const mvm_options *in, mvm_options &out);
+// dynamic LDS above 64 KiB needs the kernel's opt-in; MVM_OK or MVM_ERR_HIP
+int mvm_raise_dynamic_lds(const void *kernel, size_t bytes);
+// an option bounding a kernel class: 0 = dflt, negative = off (0), at most cap
+int mvm_resolve_limit(int32_t opt, int dflt, int cap);
+// workgroups the device holds at once (CUs x occupancy), 0 if a query fails
+int64_t mvm_coresident_blocks(const void *kernel, int threads, size_t lds);
+// The LSAP plans' loop: n + 1 offsets of the workspace regions and the output
+// pairs; need(nr, nc, tr, elem) = region of a non-empty nr <= nc problem (tr:
+// given tall).  The workspace total, or -1 with "<who>: ..." recorded.
+int64_t mvm_lsap_plan_offsets(const char *who, int32_t n, const int64_t *rows, const int64_t *cols,
+                              size_t elem, int64_t (*need)(int64_t nr, int64_t nc, bool tr, size_t elem),
+                              int64_t *ws_offs, int64_t *out_offs);

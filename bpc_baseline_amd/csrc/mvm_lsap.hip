@@ -31,6 +31,7 @@
 #include "mvmatch.h"
 #include "mvm_internal.h"
 #include "mvm_lsap_sparse.h"
+#include "mvm_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -41,16 +42,7 @@ constexpr int kLsapWaves = kLsapThreads / 64;
 constexpr int kTile = 64;   // transpose tile
 constexpr int kScanU = 4;   // columns per thread whose loads are batched in a Dijkstra scan
 
-struct LsapArgs {
-    const void *cost;           // float or double (the kernels' CT)
-    const int64_t *cost_offs;   // element offset of each problem's matrix
-    const int64_t *dims;        // [n][2]: rows, cols (row-major, ld = cols)
-    const int64_t *ws_offs;     // byte offset of each problem's workspace
-    unsigned char *ws;
-    const int64_t *out_offs;    // offset of each problem's min(rows, cols) output pairs
-    int64_t *row_ind;
-    int64_t *col_ind;
-    int32_t *status;            // 0 ok, 1 invalid entries (NaN / -inf), 2 infeasible
+struct LsapArgs : LsapIo {
     int32_t wave_max_cols;      // problems with max(rows, cols) <= this run in lsap_wave_kernel
     int32_t multi_g;            // > 1: larger problems run in lsap_multi_kernel, G workgroups each
     int32_t mid_max_cols;       // long sides in (wave_max_cols, this]: 256-thread lsap_kernel
@@ -101,6 +93,14 @@ struct Red {
     double m;      // smallest shortest-path cost seen
     int32_t first; // smallest scan position holding m
     int32_t last_free;   // largest scan position holding m with an unassigned column (-1: none)
+
+    template <int CTRL>
+    __device__ static Red dpp(const Red &r) {
+        return {dpp_mov<CTRL>(r.m), dpp_mov<CTRL>(r.first), dpp_mov<CTRL>(r.last_free)};
+    }
+    __device__ static Red lane(const Red &r, int l) {
+        return {read_lane(r.m, l), read_lane(r.first, l), read_lane(r.last_free, l)};
+    }
 };
 
 __device__ __forceinline__ Red red_combine(Red a, Red b) {
@@ -109,45 +109,6 @@ __device__ __forceinline__ Red red_combine(Red a, Red b) {
     a.first = min(a.first, b.first);
     a.last_free = max(a.last_free, b.last_free);
     return a;
-}
-
-// Wave reduction with DPP: four row-local steps (quad_perm [1,0,3,2],
-// quad_perm [2,3,0,1], row_half_mirror, row_mirror) leave every lane of a
-// 16-lane row with the row's result; the four rows are then combined on the
-// scalar unit from v_readlane.  No LDS round trips (a shuffle is a bpermute).
-template <int CTRL>
-__device__ __forceinline__ Red red_dpp_step(Red r) {
-    const uint64_t mb = (uint64_t)__double_as_longlong(r.m);
-    const int lo = __builtin_amdgcn_update_dpp((int)(uint32_t)mb, (int)(uint32_t)mb, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(uint32_t)(mb >> 32), (int)(uint32_t)(mb >> 32), CTRL,
-                                               0xF, 0xF, false);
-    Red o;
-    o.m = __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-    o.first = __builtin_amdgcn_update_dpp(r.first, r.first, CTRL, 0xF, 0xF, false);
-    o.last_free = __builtin_amdgcn_update_dpp(r.last_free, r.last_free, CTRL, 0xF, 0xF, false);
-    return red_combine(r, o);
-}
-
-__device__ __forceinline__ Red red_readlane(const Red &r, int l) {
-    const uint64_t mb = (uint64_t)__double_as_longlong(r.m);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mb, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mb >> 32), l);
-    Red o;
-    o.m = __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-    o.first = __builtin_amdgcn_readlane(r.first, l);
-    o.last_free = __builtin_amdgcn_readlane(r.last_free, l);
-    return o;
-}
-
-__device__ __forceinline__ Red red_wave_dpp(Red r) {
-    r = red_dpp_step<0xB1>(r);
-    r = red_dpp_step<0x4E>(r);
-    r = red_dpp_step<0x141>(r);
-    r = red_dpp_step<0x140>(r);
-    Red a = red_readlane(r, 0);
-    a = red_combine(a, red_readlane(r, 16));
-    a = red_combine(a, red_readlane(r, 32));
-    return red_combine(a, red_readlane(r, 48));
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -340,7 +301,7 @@ __global__ __launch_bounds__(NT) void lsap_kernel(LsapArgs a) {
                     }
                 }
             }
-            best = red_wave_dpp(best);   // 6% faster than a shuffle butterfly at 576 x 24
+            best = wave_reduce(best, red_combine);   // 6% faster than a shuffle butterfly at 576 x 24
             if (lane == 0) s_red[wave] = best;
             __syncthreads();
             if (t == 0) {
@@ -430,7 +391,7 @@ __global__ __launch_bounds__(NT) void lsap_kernel(LsapArgs a) {
 // col4row[i] == j -- so no SR list is needed.
 constexpr int kWaveMaxK = 16;              // columns per lane -> long side <= 1024
 constexpr int kWaveProblems = 4;           // waves (problems) per workgroup
-constexpr int kWaveMaxCols = 64 * kWaveMaxK;
+static_assert(kWaveMaxCols == 64 * kWaveMaxK, "mvm_lsap_sparse.h's bound of the class");
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -534,7 +495,7 @@ __device__ __forceinline__ void lsap_wave_solve(const LsapArgs &a, int p, int64_
                     if (free_col) best.last_free = max(best.last_free, pos[q]);
                 }
             }
-            best = red_wave_dpp(best);   // 6% faster than a shuffle butterfly at 576 x 24
+            best = wave_reduce(best, red_combine);   // 6% faster than a shuffle butterfly at 576 x 24
             if (!(best.m < INFINITY)) {
                 if (lane == 0) a.status[p] = 2;   // infeasible
                 return;
@@ -885,7 +846,7 @@ __global__ __launch_bounds__(NT, OCC) void lsap_reg_kernel(LsapArgs a) {
                     if (fr) best.last_free = max(best.last_free, key);
                 }
             }
-            best = red_wave_dpp(best);
+            best = wave_reduce(best, red_combine);
             if (lane == 0) s_rec[par][wave] = best;
             __syncthreads();
             // every wave combines the kNW records: lane k < kNW reads record k,
@@ -893,11 +854,11 @@ __global__ __launch_bounds__(NT, OCC) void lsap_reg_kernel(LsapArgs a) {
             // associative), so every wave holds the same result
             Red r{INFINITY, 0x7FFFFFFF, -1};
             if (lane < kNW) r = s_rec[par][lane];
-            r = red_dpp_step<0xB1>(r);
-            r = red_dpp_step<0x4E>(r);
-            if (kNW > 4) r = red_dpp_step<0x141>(r);
-            if (kNW > 8) r = red_dpp_step<0x140>(r);
-            r = red_readlane(r, 0);
+            r = wave_reduce_step<0xB1>(r, red_combine);
+            r = wave_reduce_step<0x4E>(r, red_combine);
+            if (kNW > 4) r = wave_reduce_step<0x141>(r, red_combine);
+            if (kNW > 8) r = wave_reduce_step<0x140>(r, red_combine);
+            r = Red::lane(r, 0);
             par ^= 1;
             if (!(r.m < INFINITY)) {              // uniform over the workgroup
                 if (t == 0) a.status[p] = 2;      // infeasible
@@ -1236,6 +1197,14 @@ constexpr int kMregMaxCols = kMultiMaxG * kMregCols;     // 65,536
 struct URed {
     double m;
     uint32_t first, last_free;
+
+    template <int CTRL>
+    __device__ static URed dpp(const URed &r) {
+        return {dpp_mov<CTRL>(r.m), dpp_mov<CTRL>(r.first), dpp_mov<CTRL>(r.last_free)};
+    }
+    __device__ static URed lane(const URed &r, int l) {
+        return {read_lane(r.m, l), read_lane(r.first, l), read_lane(r.last_free, l)};
+    }
 };
 
 __device__ __forceinline__ URed ured_combine(URed a, const URed &b) {
@@ -1246,46 +1215,6 @@ __device__ __forceinline__ URed ured_combine(URed a, const URed &b) {
     return a;
 }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    const int lo = __builtin_amdgcn_update_dpp((int)(uint32_t)b, (int)(uint32_t)b, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(uint32_t)(b >> 32), (int)(uint32_t)(b >> 32), CTRL,
-                                               0xF, 0xF, false);
-    return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp32(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xF, 0xF, false);
-}
-
-template <int CTRL>
-__device__ __forceinline__ URed ured_dpp_step(URed r) {
-    URed o{dpp64<CTRL>(r.m), dpp32<CTRL>(r.first), dpp32<CTRL>(r.last_free)};
-    return ured_combine(r, o);
-}
-
-__device__ __forceinline__ URed ured_readlane(const URed &r, int l) {
-    const uint64_t mb = (uint64_t)__double_as_longlong(r.m);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mb, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mb >> 32), l);
-    return URed{__longlong_as_double((long long)(((uint64_t)hi << 32) | lo)),
-                (uint32_t)__builtin_amdgcn_readlane((int)r.first, l),
-                (uint32_t)__builtin_amdgcn_readlane((int)r.last_free, l)};
-}
-
-__device__ __forceinline__ URed ured_wave(URed r) {
-    r = ured_dpp_step<0xB1>(r);
-    r = ured_dpp_step<0x4E>(r);
-    r = ured_dpp_step<0x141>(r);
-    r = ured_dpp_step<0x140>(r);
-    URed a = ured_readlane(r, 0);
-    a = ured_combine(a, ured_readlane(r, 16));
-    a = ured_combine(a, ured_readlane(r, 32));
-    return ured_combine(a, ured_readlane(r, 48));
-}
-
 // one workgroup's record; ps = path step of `first` | of `last_free` << 16
 struct alignas(16) XRed {
     double m;
@@ -1293,6 +1222,17 @@ struct alignas(16) XRed {
     int32_t first_r4;
     uint32_t ps;
     uint32_t pad[2];
+
+    template <int CTRL>
+    __device__ static XRed dpp(const XRed &r) {
+        XRed o = r;
+        o.m = dpp_mov<CTRL>(r.m);
+        o.first = dpp_mov<CTRL>(r.first);
+        o.last_free = dpp_mov<CTRL>(r.last_free);
+        o.first_r4 = dpp_mov<CTRL>(r.first_r4);
+        o.ps = dpp_mov<CTRL>(r.ps);
+        return o;
+    }
 };
 
 __device__ __forceinline__ XRed xred_combine(XRed a, const XRed &b) {
@@ -1308,17 +1248,6 @@ __device__ __forceinline__ XRed xred_combine(XRed a, const XRed &b) {
         a.ps = (a.ps & 0xFFFFu) | (b.ps & 0xFFFF0000u);
     }
     return a;
-}
-
-template <int CTRL>
-__device__ __forceinline__ XRed xred_dpp_step(XRed r) {
-    XRed o = r;
-    o.m = dpp64<CTRL>(r.m);
-    o.first = dpp32<CTRL>(r.first);
-    o.last_free = dpp32<CTRL>(r.last_free);
-    o.first_r4 = (int32_t)dpp32<CTRL>((uint32_t)r.first_r4);
-    o.ps = dpp32<CTRL>(r.ps);
-    return xred_combine(r, o);
 }
 
 // Records travel as tagged granules (MI355X_MICROARCH.md, hand-off R2): each
@@ -1576,7 +1505,7 @@ __global__ __launch_bounds__(kMregNT, 4) void lsap_mreg_kernel(LsapArgs a, int32
                         if (fr && key > best.last_free) best.last_free = key;
                     }
                 }
-                best = ured_wave(best);
+                best = wave_reduce(best, ured_combine);
                 MREG_PT(1);                                  // row load + scan + wave reduction
                 if (lane == 0) s_rec[wave] = best;
                 __syncthreads();
@@ -1585,10 +1514,10 @@ __global__ __launch_bounds__(kMregNT, 4) void lsap_mreg_kernel(LsapArgs a, int32
                 if (wave == 0) {                             // publish this workgroup's record
                     URed w{INFINITY, ~0u, 0u};
                     if (lane < kNW) w = s_rec[lane];
-                    w = ured_dpp_step<0xB1>(w);
-                    w = ured_dpp_step<0x4E>(w);
-                    w = ured_dpp_step<0x141>(w);
-                    w = ured_readlane(w, 0);
+                    w = wave_reduce_step<0xB1>(w, ured_combine);
+                    w = wave_reduce_step<0x4E>(w, ured_combine);
+                    w = wave_reduce_step<0x141>(w, ured_combine);
+                    w = URed::lane(w, 0);
                     uint32_t f_r4 = ~0u, ps = 0u;            // row4col -1 when no candidate
                     if (w.first != ~0u) {
                         const int jl = (int)(w.first & 0xFFFFu) - c0;
@@ -1596,8 +1525,7 @@ __global__ __launch_bounds__(kMregNT, 4) void lsap_mreg_kernel(LsapArgs a, int32
                         ps = s_ps[jl];
                     }
                     if (w.last_free != 0u) ps |= (uint32_t)s_ps[(int)(w.last_free & 0xFFFFu) - c0] << 16;
-                    const uint64_t mb = (uint64_t)__double_as_longlong(w.m);
-                    const uint32_t val = lane == 0 ? (uint32_t)mb : lane == 1 ? (uint32_t)(mb >> 32)
+                    const uint32_t val = lane == 0 ? f64_lo(w.m) : lane == 1 ? f64_hi(w.m)
                                        : lane == 2 ? w.first : lane == 3 ? w.last_free : lane == 4 ? f_r4 : ps;
                     xsync_publish(sb, par, g, lane, tag, val);
                 }
@@ -1611,26 +1539,21 @@ __global__ __launch_bounds__(kMregNT, 4) void lsap_mreg_kernel(LsapArgs a, int32
 #endif
                 XRed r{INFINITY, ~0u, 0u, -1, 0u, {0u, 0u}};
                 if (lane < G) {
-                    r.m = __longlong_as_double((long long)(((uint64_t)f[1] << 32) | f[0]));
+                    r.m = f64_of(f[0], f[1]);
                     r.first = f[2];
                     r.last_free = f[3];
                     r.first_r4 = (int32_t)f[4];
                     r.ps = f[5];
                 }
-                r = xred_dpp_step<0xB1>(r);
-                r = xred_dpp_step<0x4E>(r);
-                if (G > 4) r = xred_dpp_step<0x141>(r);
-                if (G > 8) r = xred_dpp_step<0x140>(r);
-                {
-                    const uint64_t mb = (uint64_t)__double_as_longlong(r.m);
-                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)mb);
-                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(mb >> 32));
-                    r.m = __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-                    r.first = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.first);
-                    r.last_free = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.last_free);
-                    r.first_r4 = __builtin_amdgcn_readfirstlane(r.first_r4);
-                    r.ps = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.ps);
-                }
+                r = wave_reduce_step<0xB1>(r, xred_combine);
+                r = wave_reduce_step<0x4E>(r, xred_combine);
+                if (G > 4) r = wave_reduce_step<0x141>(r, xred_combine);
+                if (G > 8) r = wave_reduce_step<0x140>(r, xred_combine);
+                r.m = first_lane(r.m);
+                r.first = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.first);
+                r.last_free = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.last_free);
+                r.first_r4 = __builtin_amdgcn_readfirstlane(r.first_r4);
+                r.ps = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.ps);
                 par ^= 1;
                 if (!(r.m < INFINITY)) break;                // infeasible (uniform over the slot)
                 const bool use_free = r.last_free != 0u;
@@ -1741,213 +1664,222 @@ timeout:
     }
 }
 
-// Launch every kernel class of the batch for cost element type CT.
+// ---- launches: one function per kernel class, called by lsap_launch in the
+// order the kernels go to the stream.  The facts they share:
+struct LsapBatch {
+    int32_t n;                 // problems
+    size_t sync_bytes;         // of the barrier + reduction slots at a.sync
+    int64_t long_min, long_max, short_max;   // over the non-empty problems (0, 0: all empty)
+    int wave_max;              // long sides up to this are the one-wave class's
+    bool empty_done;           // a launched kernel writes status 0 for the empty problems
+    bool big;                  // some problem is left for the workgroup kernels
+    const mvm_options &o;
+    hipStream_t s;
+    // classes that cannot have work are not launched
+    bool overlaps(int64_t lo, int64_t hi) const { return long_max >= lo && long_min <= hi; }
+};
+
+// Candidate-list kernels (mvm_lsap_sparse.hip) for wide problems: long sides
+// >= lsap_sparse_min_cols (default kSparseMinCols), <= 65,536, short sides
+// <= 1,024.  They also write status 0 for the empty problems.
 template <typename CT>
-int lsap_launch(LsapArgs a, int32_t n_problems, size_t sync_bytes, int64_t long_min,
-                int64_t long_max, int64_t short_max, const mvm_options &o, hipStream_t s) {
-    // long sides up to wave_max: the one-wave-per-problem kernel (default
-    // 1024, -1 = never, capped at 1024)
-    int wave_max = o.lsap_wave_max_cols == 0 ? kWaveMaxCols : o.lsap_wave_max_cols;
-    wave_max = wave_max < 0 ? 0 : (wave_max > kWaveMaxCols ? kWaveMaxCols : wave_max);
-    a.wave_max_cols = wave_max;
-    // long_min / long_max bound max(rows, cols) over the non-empty problems
-    // (long_max 0: all empty): kernel classes that cannot have work are not
-    // launched.  Every class writes status 0 for empty problems.
-    if (long_max < 1) {
-        long_min = long_max = 0;
-    }
-    auto overlaps = [&](int64_t lo, int64_t hi) { return long_max >= lo && long_min <= hi; };
-    // candidate-list kernels (mvm_lsap_sparse.hip) for wide problems: long
-    // sides >= lsap_sparse_min_cols (default kSparseMinCols), <= 65,536, short
-    // sides <= 1,024.  They also write status 0 for the empty problems.
-    bool empty_done = false, sparse_all = false;
-    {
-        const int sp_lo = o.lsap_sparse_min_cols == 0 ? kSparseMinCols
-                                                      : (o.lsap_sparse_min_cols < 0 ? 0 : o.lsap_sparse_min_cols);
-        const int64_t s_max = short_max < long_max ? short_max : long_max;
-        if (sp_lo > 0 && long_max >= sp_lo && long_max > wave_max && s_max >= 1) {
-            a.sparse_lo = sp_lo;
-            LsapSparseArgs sa{a.cost, a.cost_offs, a.dims, a.ws_offs, a.ws, a.out_offs, a.row_ind,
-                              a.col_ind, a.status, sp_lo, wave_max,
-                              (int32_t)(s_max < kSpMaxShort ? s_max : kSpMaxShort),
-                              a.bmin8, a.bmin8_offs, a.segs,
-                              o.lsap_sparse_blocks ? o.lsap_sparse_blocks : kSpTB};
-            const int st = sizeof(CT) == 8 ? lsap_sparse_launch_f64(sa, n_problems, long_max, s)
-                                            : lsap_sparse_launch_f32(sa, n_problems, long_max, s);
-            if (st != MVM_OK) return st;
-            empty_done = true;
-            // every non-empty problem is the class's: no other class has work
-            sparse_all = long_min >= sp_lo && long_min > wave_max && long_max <= kSpMaxCols &&
-                         short_max <= kSpMaxShort;
-        }
-    }
-    const dim3 wgrid((unsigned)((n_problems + kWaveProblems - 1) / kWaveProblems));
-    const dim3 wblock(64 * kWaveProblems);
-    if (wave_max > 0) {
-        if (overlaps(0, 64) || (long_max == 0 && !empty_done)) {
-            lsap_wave_kernel<CT, 1><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
-        }
-        // every instantiation also writes status 0 for the empty problems, so
-        // any one launched spares the workgroup kernel's launch for them
-        if (wave_max > 64 && overlaps(65, 128)) {
-            lsap_wave_kernel<CT, 2><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
-        }
-        if (wave_max > 128 && overlaps(129, 256)) {
-            lsap_wave_kernel<CT, 4><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
-        }
-        if (wave_max > 256 && overlaps(257, 512)) {
-            lsap_wave_kernel<CT, 8><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
-        }
+int launch_lists(LsapArgs &a, LsapBatch &b) {
+    const int sp_lo = mvm_resolve_limit(b.o.lsap_sparse_min_cols, kSparseMinCols, INT32_MAX);
+    const int64_t s_max = b.short_max < b.long_max ? b.short_max : b.long_max;
+    if (!(sp_lo > 0 && b.long_max >= sp_lo && b.long_max > b.wave_max && s_max >= 1)) return MVM_OK;
+    a.sparse_lo = sp_lo;
+    LsapSparseArgs sa{};
+    static_cast<LsapIo &>(sa) = a;
+    sa.lo = sp_lo;
+    sa.wave_max = b.wave_max;
+    sa.s_cap = (int32_t)(s_max < kSpMaxShort ? s_max : kSpMaxShort);
+    sa.bmin8 = a.bmin8;
+    sa.bmin8_offs = a.bmin8_offs;
+    sa.segs = a.segs;
+    sa.tb = b.o.lsap_sparse_blocks ? b.o.lsap_sparse_blocks : kSpTB;
+    const int st = sizeof(CT) == 8 ? lsap_sparse_launch_f64(sa, b.n, b.long_max, b.s)
+                                    : lsap_sparse_launch_f32(sa, b.n, b.long_max, b.s);
+    if (st != MVM_OK) return st;
+    b.empty_done = true;
+    // every non-empty problem is the class's: no other class has work
+    if (b.long_min >= sp_lo && b.long_min > b.wave_max && b.long_max <= kSpMaxCols && b.short_max <= kSpMaxShort)
+        b.big = false;
+    return MVM_OK;
+}
+
+// One wave per problem: each instantiation owns the long sides [lo, hi], hi / 64
+// columns per lane.  Every one writes status 0 for the empty problems, so any
+// one launched spares the workgroup kernel's launch (all empty: the first).
+template <typename CT>
+void launch_wave(const LsapArgs &a, LsapBatch &b) {
+    const struct {
+        void (*kern)(LsapArgs, int32_t);
+        int lo, hi;
+    } classes[] = {
+        {lsap_wave_kernel<CT, 1>, 0, 64},
+        {lsap_wave_kernel<CT, 2>, 65, 128},
+        {lsap_wave_kernel<CT, 4>, 129, 256},
+        {lsap_wave_kernel<CT, 8>, 257, 512},
         // 12 columns per lane for long sides of 513-768 (576 x 24 at 24
         // detections per view): a quarter fewer slots per Dijkstra step than 16
-        if (wave_max > 512 && overlaps(513, 768)) {
-            lsap_wave_kernel<CT, 12, 512><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
+        {lsap_wave_kernel<CT, 12, 512>, 513, 768},
+        {lsap_wave_kernel<CT, 16, 768>, 769, 1024},
+    };
+    const dim3 grid((unsigned)((b.n + kWaveProblems - 1) / kWaveProblems)), block(64 * kWaveProblems);
+    for (const auto &c : classes)
+        if (b.wave_max > 0 && b.wave_max >= c.lo && b.overlaps(c.lo, c.hi)) {
+            c.kern<<<grid, block, 0, b.s>>>(a, b.n);
+            b.empty_done = true;
         }
-        if (wave_max > 768 && overlaps(769, 1024)) {
-            lsap_wave_kernel<CT, 16, 768><<<wgrid, wblock, 0, s>>>(a, n_problems);
-            empty_done = true;
-        }
-    }
-    const bool big = long_max > wave_max && !sparse_all;   // anything left for the workgroup kernels
-    int reg_max = o.lsap_reg_max_cols == 0 ? kRegMaxCols : o.lsap_reg_max_cols;
-    reg_max = reg_max < 0 ? 0 : (reg_max > kRegMaxCols ? kRegMaxCols : reg_max);
-    a.reg_max_cols = reg_max > wave_max ? reg_max : 0;
-    // long sides in (max(wave_max, reg_max), lsap_mreg_max_cols] with short
-    // sides <= 1024: G = ceil(long / 4096) workgroups per problem with the
-    // column state in registers, persistent slots of G co-resident workgroups
-    int mreg_max = o.lsap_mreg_max_cols == 0 ? kMregMaxCols : o.lsap_mreg_max_cols;
-    mreg_max = mreg_max < 0 ? 0 : (mreg_max > kMregMaxCols ? kMregMaxCols : mreg_max);
-    a.mreg_lo = wave_max > a.reg_max_cols ? wave_max : a.reg_max_cols;
-    if (big && mreg_max > a.mreg_lo && overlaps((int64_t)a.mreg_lo + 1, mreg_max)) {
-        const int64_t hi = long_max < mreg_max ? long_max : mreg_max;
-        const int mg = (int)((hi + kMregCols - 1) / kMregCols);
-        const int cap = (int)(long_max < kRegMaxShort ? long_max : kRegMaxShort);
-        const size_t lds = mreg_lds_bytes(cap);
-        const void *kern = reinterpret_cast<const void *>(&lsap_mreg_kernel<CT>);
-        int occ = 0, cus = 0, dev = 0;
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, kMregNT, lds) == hipSuccess) {
-            // slots in whole groups of 8 (one per XCD): the grid never exceeds co-residency
-            const int64_t per_xcd = (int64_t)cus * occ / (8 * mg);
-            const int64_t slots = per_xcd * 8 < n_problems ? per_xcd * 8 : n_problems;
-            if (slots >= 1) {
-                a.mreg_g = mg;
-                a.mreg_slots = (int32_t)slots;
-                a.mreg_max_cols = mreg_max;
-                a.mreg_nr_cap = cap;
-                if (hipMemsetAsync(a.sync, 0, sync_bytes, s) != hipSuccess)
-                    return mvm_fail(MVM_ERR_HIP, "hipMemsetAsync(lsap sync) failed");
-                int32_t n_arg = n_problems;
-                void *params[] = {&a, &n_arg};
-                const dim3 grid((unsigned)(8 * mg * ((slots + 7) / 8))), block(kMregNT);
-                if (hipLaunchCooperativeKernel(kern, grid, block, params, (unsigned)lds, s) != hipSuccess) {
-                    (void)hipGetLastError();
-                    a.mreg_g = 0;                  // the other classes take these problems
-                }
-            }
-        }
-    }
-    // Few large problems: G co-resident workgroups per problem (cooperative
-    // launch guarantees co-residency).  Default: as many workgroups per
-    // problem as the chip holds, up to 16, when that is at least 2; -1 off.
-    int G = o.lsap_multi_g == 0 ? -1 : (o.lsap_multi_g < 0 ? 0 : o.lsap_multi_g);
-    const int64_t groups8 = ((int64_t)n_problems + 7) / 8;     // problems per XCD slot
-    int occ = 0, cus = 0, dev = 0;
-    if (G != 0 && G != 1 && big && hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(&lsap_multi_kernel<CT>),
-                                                     kLsapThreads, 0) == hipSuccess) {
-        const int64_t capacity = (int64_t)cus * occ;
-        const int64_t fit = capacity / (8 * groups8);
+}
+
+// Zero the sync slots, then one cooperative launch of kern(a, n).  launched =
+// false: the runtime refused it, the other classes take the problems.
+int launch_cooperative(const void *kern, unsigned blocks, int threads, size_t lds, LsapArgs &a,
+                       const LsapBatch &b, bool &launched) {
+    launched = true;   // (an error return ends the launch)
+    if (hipMemsetAsync(a.sync, 0, b.sync_bytes, b.s) != hipSuccess)
+        return mvm_fail(MVM_ERR_HIP, "hipMemsetAsync(lsap sync) failed");
+    int32_t n_arg = b.n;
+    void *params[] = {&a, &n_arg};
+    const hipError_t e = hipLaunchCooperativeKernel(kern, dim3(blocks), dim3(threads), params, (unsigned)lds, b.s);
+    if (!(launched = e == hipSuccess)) (void)hipGetLastError();
+    return MVM_OK;
+}
+
+// Long sides in (mreg_lo, lsap_mreg_max_cols], short sides <= 1024: ceil(long / 4096)
+// workgroups per problem, column state in registers, persistent co-resident slots.
+template <typename CT>
+int launch_mreg(LsapArgs &a, const LsapBatch &b) {
+    const int mreg_max = mvm_resolve_limit(b.o.lsap_mreg_max_cols, kMregMaxCols, kMregMaxCols);
+    if (!(b.big && mreg_max > a.mreg_lo && b.overlaps((int64_t)a.mreg_lo + 1, mreg_max))) return MVM_OK;
+    const int64_t hi = b.long_max < mreg_max ? b.long_max : mreg_max;
+    const int mg = (int)((hi + kMregCols - 1) / kMregCols);
+    const int cap = (int)(b.long_max < kRegMaxShort ? b.long_max : kRegMaxShort);
+    const size_t lds = mreg_lds_bytes(cap);
+    const void *kern = reinterpret_cast<const void *>(&lsap_mreg_kernel<CT>);
+    if (const int st = mvm_raise_dynamic_lds(kern, lds)) return st;
+    // slots in whole groups of 8 (one per XCD): the grid never exceeds co-residency
+    const int64_t per_xcd = mvm_coresident_blocks(kern, kMregNT, lds) / (8 * mg);
+    const int64_t slots = per_xcd * 8 < b.n ? per_xcd * 8 : b.n;
+    if (slots < 1) return MVM_OK;
+    a.mreg_g = mg;
+    a.mreg_slots = (int32_t)slots;
+    a.mreg_max_cols = mreg_max;
+    a.mreg_nr_cap = cap;
+    bool launched;
+    const int st = launch_cooperative(kern, (unsigned)(8 * mg * ((slots + 7) / 8)), kMregNT, lds, a, b, launched);
+    if (!launched) a.mreg_g = 0;                   // the other classes take these problems
+    return st;
+}
+
+// Few large problems: G co-resident workgroups per problem.  Default: as many
+// per problem as the chip holds, up to 16, when that is at least 2; -1 off.
+template <typename CT>
+int launch_multi(LsapArgs &a, const LsapBatch &b) {
+    int G = b.o.lsap_multi_g == 0 ? -1 : (b.o.lsap_multi_g < 0 ? 0 : b.o.lsap_multi_g);
+    const int64_t groups8 = ((int64_t)b.n + 7) / 8;     // problems per XCD slot
+    const void *kern = reinterpret_cast<const void *>(&lsap_multi_kernel<CT>);
+    if (G != 0 && G != 1 && b.big) {
+        const int64_t fit = mvm_coresident_blocks(kern, kLsapThreads, 0) / (8 * groups8);
         if (G < 0) G = (int)(fit > kMultiMaxG ? kMultiMaxG : fit);
         if (G > kMultiMaxG) G = kMultiMaxG;
         if ((int64_t)G > fit) G = (int)fit;   // never exceed co-residency
     } else {
         G = 0;
     }
-    if (G >= 2 && big) {
-        a.multi_g = G;
-        if (hipMemsetAsync(a.sync, 0, sync_bytes, s) != hipSuccess)
-            return mvm_fail(MVM_ERR_HIP, "hipMemsetAsync(lsap sync) failed");
-        int32_t n_arg = n_problems;
-        void *params[] = {&a, &n_arg};
-        const dim3 grid((unsigned)(8 * G * groups8)), block(kLsapThreads);
-        if (hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&lsap_multi_kernel<CT>), grid, block,
-                                       params, 0, s) != hipSuccess) {
-            (void)hipGetLastError();
-            a.multi_g = 0;                     // fall back to one workgroup per problem
-        }
-    }
-    // long sides in (wave_max, lsap_reg_max_cols] with short sides <= 1024:
-    // one workgroup per problem with the column state in registers
-    if (a.multi_g <= 1 && big && a.reg_max_cols > 0 && overlaps((int64_t)wave_max + 1, a.reg_max_cols)) {
-        a.reg_nc_cap = (int32_t)(long_max < a.reg_max_cols ? long_max : a.reg_max_cols);
-        a.reg_nr_cap = (int32_t)(long_max < kRegMaxShort ? long_max : kRegMaxShort);
-        const size_t lds = (size_t)a.reg_nc_cap * 8 + (size_t)a.reg_nr_cap * 12;
-        // 512 threads x 8 columns: ~100 VGPRs, two workgroups per CU
-        const bool wide = o.lsap_reg_threads == 1024;
-        if (o.lsap_reg_threads != 0 && o.lsap_reg_threads != 512 && !wide)
-            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "lsap_reg_threads %d not 512 or 1024",
-                            (int)o.lsap_reg_threads);
-        const void *kern = wide ? reinterpret_cast<const void *>(&lsap_reg_kernel<CT, 1024, 4>)
-                                : reinterpret_cast<const void *>(&lsap_reg_kernel<CT, 512, 8>);
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
-        if (wide)
-            lsap_reg_kernel<CT, 1024, 4><<<dim3((unsigned)n_problems), dim3(1024), lds, s>>>(a);
-        else
-            lsap_reg_kernel<CT, 512, 8><<<dim3((unsigned)n_problems), dim3(512), lds, s>>>(a);
-    }
-    // one workgroup per problem: 256 threads (8 batched columns per thread) up to
-    // lsap_mid_max_cols long-side columns, 1024 threads (4 per thread) above.
-    // MI355X: 4096 x 64 problems 4.00 vs 4.36 ms per 1000 with 256 threads;
-    // 65536 x 256: 52 vs 80 ms per 200 with 1024 (tools/tune_lsap.py)
+    if (!(G >= 2 && b.big)) return MVM_OK;
+    a.multi_g = G;
+    bool launched;
+    const int st = launch_cooperative(kern, (unsigned)(8 * G * groups8), kLsapThreads, 0, a, b, launched);
+    if (!launched) a.multi_g = 0;                  // fall back to one workgroup per problem
+    return st;
+}
+
+// Long sides in (wave_max, lsap_reg_max_cols] with short sides <= 1024:
+// one workgroup per problem with the column state in registers.
+template <typename CT>
+int launch_reg(LsapArgs &a, const LsapBatch &b) {
+    if (!(a.multi_g <= 1 && b.big && a.reg_max_cols > 0 && b.overlaps((int64_t)b.wave_max + 1, a.reg_max_cols)))
+        return MVM_OK;
+    a.reg_nc_cap = (int32_t)(b.long_max < a.reg_max_cols ? b.long_max : a.reg_max_cols);
+    a.reg_nr_cap = (int32_t)(b.long_max < kRegMaxShort ? b.long_max : kRegMaxShort);
+    const size_t lds = (size_t)a.reg_nc_cap * 8 + (size_t)a.reg_nr_cap * 12;
+    // 512 threads x 8 columns: ~100 VGPRs, two workgroups per CU
+    const bool wide = b.o.lsap_reg_threads == 1024;
+    if (b.o.lsap_reg_threads != 0 && b.o.lsap_reg_threads != 512 && !wide)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "lsap_reg_threads %d not 512 or 1024",
+                        (int)b.o.lsap_reg_threads);
+    void (*kern)(LsapArgs) = wide ? lsap_reg_kernel<CT, 1024, 4> : lsap_reg_kernel<CT, 512, 8>;
+    if (const int st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return st;
+    kern<<<dim3((unsigned)b.n), dim3(wide ? 1024 : 512), lds, b.s>>>(a);
+    return MVM_OK;
+}
+
+// Long sides in (wave_max, lsap_lds_max_cols]: one workgroup per problem with
+// the column state in LDS, 256 threads up to lsap_lds_small_cols, 1024 above.
+template <typename CT>
+int launch_lds_state(const LsapArgs &a, const LsapBatch &b) {
+    if (!(a.multi_g <= 1 && b.big && a.lds_max_cols > 0)) return MVM_OK;
+    // dynamic LDS sized for the class's longest side (the batch's when bounded)
+    auto launch = [&](void (*kern)(LsapArgs), int threads, int64_t hi) {
+        const size_t lds = (size_t)(b.long_max < hi ? b.long_max : hi) * kLdsStateBytes;
+        if (const int st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return st;
+        kern<<<dim3((unsigned)b.n), dim3(threads), lds, b.s>>>(a);
+        return (int)MVM_OK;
+    };
+    const int64_t small_hi = a.lds_small_cols < a.lds_max_cols ? a.lds_small_cols : a.lds_max_cols;
+    if (small_hi > b.wave_max && b.overlaps((int64_t)b.wave_max + 1, small_hi))
+        if (const int st = launch(lsap_kernel<CT, 256, true>, 256, small_hi)) return st;
+    const int64_t big_lo = (small_hi > b.wave_max ? small_hi : b.wave_max) + 1;
+    if (a.lds_max_cols >= big_lo && b.overlaps(big_lo, a.lds_max_cols))
+        return launch(lsap_kernel<CT, kLsapThreads, true>, kLsapThreads, a.lds_max_cols);
+    return MVM_OK;
+}
+
+// The rest, column state in the workspace: 256 threads (8 batched columns per
+// thread) up to lsap_mid_max_cols long-side columns, 1024 threads (4 per
+// thread) above.  MI355X: 4096 x 64 problems 4.00 vs 4.36 ms per 1000 with 256
+// threads; 65536 x 256: 52 vs 80 ms per 200 with 1024 (tools/tune_lsap.py).
+// The first also runs when nothing yet wrote the empty problems' status.
+template <typename CT>
+void launch_ws_state(const LsapArgs &a, const LsapBatch &b) {
+    const int64_t lo256 = (int64_t)(a.lds_max_cols > b.wave_max ? a.lds_max_cols : b.wave_max) + 1;
+    const int64_t hi256 = a.mid_max_cols;
+    if (!b.empty_done || (a.multi_g <= 1 && b.big && b.overlaps(lo256, hi256)))
+        lsap_kernel<CT, 256><<<dim3((unsigned)b.n), dim3(256), 0, b.s>>>(a);
+    if (a.multi_g <= 1 && b.big && b.long_max > (hi256 > lo256 - 1 ? hi256 : lo256 - 1))
+        lsap_kernel<CT, kLsapThreads><<<dim3((unsigned)b.n), dim3(kLsapThreads), 0, b.s>>>(a);
+}
+
+// Launch every kernel class of the batch for cost element type CT; a kernel
+// is launched with the fields of `a` decided by then.
+template <typename CT>
+int lsap_launch(LsapArgs a, int32_t n_problems, size_t sync_bytes, int64_t long_min,
+                int64_t long_max, int64_t short_max, const mvm_options &o, hipStream_t s) {
+    if (long_max < 1) long_min = long_max = 0;   // all empty
+    // the one-wave-per-problem kernel's bound (default 1024, -1 = never, capped at 1024)
+    const int wave_max = mvm_resolve_limit(o.lsap_wave_max_cols, kWaveMaxCols, kWaveMaxCols);
+    a.wave_max_cols = wave_max;
+    LsapBatch b{n_problems, sync_bytes, long_min, long_max, short_max, wave_max,
+                /*empty_done=*/false, /*big=*/long_max > wave_max, o, s};
+    int st;
+    if ((st = launch_lists<CT>(a, b))) return st;
+    launch_wave<CT>(a, b);
+    // the register-state classes: reg up to lsap_reg_max_cols, mreg above it
+    const int reg_max = mvm_resolve_limit(o.lsap_reg_max_cols, kRegMaxCols, kRegMaxCols);
+    a.reg_max_cols = reg_max > wave_max ? reg_max : 0;
+    a.mreg_lo = wave_max > a.reg_max_cols ? wave_max : a.reg_max_cols;
+    if ((st = launch_mreg<CT>(a, b))) return st;
+    if ((st = launch_multi<CT>(a, b))) return st;
+    if ((st = launch_reg<CT>(a, b))) return st;
+    // one workgroup per problem: state in LDS up to lsap_lds_max_cols, else the workspace
     a.mid_max_cols = o.lsap_mid_max_cols ? o.lsap_mid_max_cols : 8192;
-    // long sides in (wave_max, lsap_lds_max_cols]: column state in LDS
-    int lds_max = o.lsap_lds_max_cols == 0 ? kLdsMaxCols : o.lsap_lds_max_cols;
-    lds_max = lds_max < 0 ? 0 : (lds_max > kLdsMaxCols ? kLdsMaxCols : lds_max);
+    const int lds_max = mvm_resolve_limit(o.lsap_lds_max_cols, kLdsMaxCols, kLdsMaxCols);
     a.lds_max_cols = lds_max > wave_max ? lds_max : 0;
     a.lds_small_cols = o.lsap_lds_small_cols ? o.lsap_lds_small_cols : 2048;
-    if (a.multi_g <= 1 && big && a.lds_max_cols > 0) {
-        // dynamic LDS sized for the class's longest side (the batch's when bounded)
-        auto lds_for = [&](int64_t hi) {
-            return (size_t)(long_max < hi ? long_max : hi) * kLdsStateBytes;
-        };
-        const int64_t small_hi = a.lds_small_cols < a.lds_max_cols ? a.lds_small_cols : a.lds_max_cols;
-        if (small_hi > wave_max && overlaps((int64_t)wave_max + 1, small_hi)) {
-            const size_t lds = lds_for(small_hi);
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&lsap_kernel<CT, 256, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
-            lsap_kernel<CT, 256, true><<<dim3((unsigned)n_problems), dim3(256), lds, s>>>(a);
-        }
-        const int64_t big_lo = (small_hi > wave_max ? small_hi : wave_max) + 1;
-        if (a.lds_max_cols >= big_lo && overlaps(big_lo, a.lds_max_cols)) {
-            const size_t lds = lds_for(a.lds_max_cols);
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&lsap_kernel<CT, kLsapThreads, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
-            lsap_kernel<CT, kLsapThreads, true><<<dim3((unsigned)n_problems), dim3(kLsapThreads), lds, s>>>(a);
-        }
-    }
-    const int64_t lo256 = (int64_t)(a.lds_max_cols > wave_max ? a.lds_max_cols : wave_max) + 1;
-    const int64_t hi256 = a.mid_max_cols;
-    if (!empty_done || (a.multi_g <= 1 && big && overlaps(lo256, hi256)))
-        lsap_kernel<CT, 256><<<dim3((unsigned)n_problems), dim3(256), 0, s>>>(a);
-    if (a.multi_g <= 1 && big && long_max > (hi256 > lo256 - 1 ? hi256 : lo256 - 1))
-        lsap_kernel<CT, kLsapThreads><<<dim3((unsigned)n_problems), dim3(kLsapThreads), 0, s>>>(a);
+    if ((st = launch_lds_state<CT>(a, b))) return st;
+    launch_ws_state<CT>(a, b);
     return mvm_check_launch("lsap_kernel");
 }
 
@@ -1965,31 +1897,19 @@ int64_t mvm_lsap_plan_ex(int32_t n_problems, const int64_t *rows, const int64_t 
         mvm_set_error("mvm_lsap_plan: cost_dtype must be MVM_F32 or MVM_F64");
         return -1;
     }
-    const size_t elem = cost_dtype == MVM_F64 ? sizeof(double) : sizeof(float);
-    int64_t w = 0, o = 0;
-    for (int32_t p = 0; p < n_problems; ++p) {
-        if (rows[p] < 0 || cols[p] < 0 || rows[p] > 0x7FFFFFFF || cols[p] > 0x7FFFFFFF) {
-            mvm_set_error("mvm_lsap_plan: problem dimensions out of range");
-            return -1;
-        }
-        ws_offs[p] = w;
-        out_offs[p] = o;
-        const bool tr = cols[p] < rows[p];
-        const int64_t nr = tr ? cols[p] : rows[p], nc = tr ? rows[p] : cols[p];
-        // room for whichever class solves it: the dense layout, or the
-        // candidate lists of the wide class (mvm_lsap_sparse.h)
-        int64_t need = (rows[p] && cols[p]) ? (int64_t)lsap_layout(nr, nc, tr, elem).total : 0;
-        if (rows[p] && cols[p] && nc <= kSpMaxCols && nr <= kSpMaxShort) {
-            const int64_t sp = (int64_t)lsap_sparse_layout(nr, nc, elem, tr).total;
-            need = sp > need ? sp : need;
-        }
-        w += need;
-        o += rows[p] < cols[p] ? rows[p] : cols[p];
-    }
-    ws_offs[n_problems] = w;
-    out_offs[n_problems] = o;
+    // room for whichever class solves it: the dense layout, or the
+    // candidate lists of the wide class (mvm_lsap_sparse.h)
+    const auto need = [](int64_t nr, int64_t nc, bool tr, size_t elem) {
+        const int64_t dense = (int64_t)lsap_layout(nr, nc, tr, elem).total;
+        if (nc > kSpMaxCols || nr > kSpMaxShort) return dense;
+        const int64_t sp = (int64_t)lsap_sparse_layout(nr, nc, elem, tr).total;
+        return sp > dense ? sp : dense;
+    };
+    const int64_t w = mvm_lsap_plan_offsets("mvm_lsap_plan", n_problems, rows, cols,
+                                            cost_dtype == MVM_F64 ? sizeof(double) : sizeof(float), need,
+                                            ws_offs, out_offs);
     // barrier + reduction slots of lsap_multi_kernel, at the END of the workspace
-    return w + (int64_t)n_problems * (int64_t)kSyncBytes;
+    return w < 0 ? w : w + (int64_t)n_problems * (int64_t)kSyncBytes;
 }
 
 int64_t mvm_lsap_plan(int32_t n_problems, const int64_t *rows, const int64_t *cols,
@@ -2052,13 +1972,22 @@ int mvm_lsap_solve_ex3(const void *cost_dev, int32_t cost_dtype, const int64_t *
         return mvm_fail(MVM_ERR_WORKSPACE, "null workspace");
     const size_t sync_bytes = (size_t)n_problems * kSyncBytes;
     if (workspace_bytes < sync_bytes) return mvm_fail(MVM_ERR_WORKSPACE, "workspace smaller than the plan");
-    LsapArgs a{cost_dev, cost_offs_dev, dims_dev, ws_offs_dev,
-               reinterpret_cast<unsigned char *>(workspace_dev), out_offs_dev, row_ind_dev,
-               col_ind_dev, status_dev, 0, 0, 0,
-               reinterpret_cast<unsigned char *>(
-                   (reinterpret_cast<uintptr_t>(workspace_dev) + workspace_bytes - sync_bytes) &
-                   ~(uintptr_t)255),   // at or after the per-problem regions (all 256-aligned)
-               0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, bmin8_dev, bmin8_offs_dev, segs_dev};
+    LsapArgs a{};   // the classes' bounds: lsap_launch
+    a.cost = cost_dev;
+    a.cost_offs = cost_offs_dev;
+    a.dims = dims_dev;
+    a.ws_offs = ws_offs_dev;
+    a.ws = reinterpret_cast<unsigned char *>(workspace_dev);
+    a.out_offs = out_offs_dev;
+    a.row_ind = row_ind_dev;
+    a.col_ind = col_ind_dev;
+    a.status = status_dev;
+    // at or after the per-problem regions (all 256-aligned)
+    a.sync = reinterpret_cast<unsigned char *>(
+        (reinterpret_cast<uintptr_t>(workspace_dev) + workspace_bytes - sync_bytes) & ~(uintptr_t)255);
+    a.bmin8 = bmin8_dev;
+    a.bmin8_offs = bmin8_offs_dev;
+    a.segs = segs_dev;
     if (bmin8_dev && (!bmin8_offs_dev || !segs_dev))
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "bmin8 needs its offsets and segment lengths");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

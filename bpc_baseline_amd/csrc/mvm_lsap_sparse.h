@@ -18,17 +18,23 @@ constexpr int kSpTileCols = 2048;    // columns per block-minimum workgroup
 // the register-state workgroup; 3136 x 56 1.42 against 1.38, 2304 x 48 1.12
 // against 1.03 (tools/bench_lsap.py, profiles/r05/lsap_sparse/)
 constexpr int kSparseMinCols = 4096;
+// one-wave class (lsap_wave_kernel): default and cap of mvm_options.lsap_wave_max_cols
+constexpr int kWaveMaxCols = 1024;
 
-struct LsapSparseArgs {
-    const void *cost;             // float or double (CT)
-    const int64_t *cost_offs;
-    const int64_t *dims;          // [n][2] rows, cols
-    const int64_t *ws_offs;
+// the batch as every assignment kernel is given it
+struct LsapIo {
+    const void *cost;           // float or double (the kernels' CT)
+    const int64_t *cost_offs;   // element offset of each problem's matrix
+    const int64_t *dims;        // [n][2]: rows, cols (row-major, ld = cols)
+    const int64_t *ws_offs;     // byte offset of each problem's workspace
     unsigned char *ws;
-    const int64_t *out_offs;
+    const int64_t *out_offs;    // offset of each problem's min(rows, cols) output pairs
     int64_t *row_ind;
     int64_t *col_ind;
-    int32_t *status;
+    int32_t *status;            // 0 ok, 1 invalid entries (NaN / -inf), 2 infeasible
+};
+
+struct LsapSparseArgs : LsapIo {
     int32_t lo;                   // long sides >= lo (> wave_max, <= kSpMaxCols) with short
     int32_t wave_max;             // sides in [1, kSpMaxShort] are this class's
     int32_t s_cap;                // LDS sizing: every short side of the class is <= this

@@ -72,65 +72,7 @@ __device__ __forceinline__ bool sp_invalid(CT v) {
     return (v != v) || (v == -(CT)INFINITY);
 }
 
-// ---- wave / workgroup reductions (DPP row steps, then the four rows) -------
-
-template <int CTRL>
-__device__ __forceinline__ double sp_dpp_f64(double x) {
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    const int lo = __builtin_amdgcn_update_dpp((int)(uint32_t)b, (int)(uint32_t)b, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(uint32_t)(b >> 32), (int)(uint32_t)(b >> 32), CTRL,
-                                               0xF, 0xF, false);
-    return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
-__device__ __forceinline__ double sp_readlane_f64(double x, int l) {
-    const uint64_t b = (uint64_t)__double_as_longlong(x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// minimum over the wave (values are never NaN), uniform
-__device__ __forceinline__ double sp_wave_min(double x) {
-    x = fmin(x, sp_dpp_f64<0xB1>(x));
-    x = fmin(x, sp_dpp_f64<0x4E>(x));
-    x = fmin(x, sp_dpp_f64<0x141>(x));
-    x = fmin(x, sp_dpp_f64<0x140>(x));
-    return fmin(fmin(sp_readlane_f64(x, 0), sp_readlane_f64(x, 16)),
-                fmin(sp_readlane_f64(x, 32), sp_readlane_f64(x, 48)));
-}
-
-template <int CTRL>
-__device__ __forceinline__ int sp_dpp_i32(int x) {
-    return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xF, 0xF, false);
-}
-
-__device__ __forceinline__ int sp_wave_min_i32(int x) {
-    x = min(x, sp_dpp_i32<0xB1>(x));
-    x = min(x, sp_dpp_i32<0x4E>(x));
-    x = min(x, sp_dpp_i32<0x141>(x));
-    x = min(x, sp_dpp_i32<0x140>(x));
-    return min(min(__builtin_amdgcn_readlane(x, 0), __builtin_amdgcn_readlane(x, 16)),
-               min(__builtin_amdgcn_readlane(x, 32), __builtin_amdgcn_readlane(x, 48)));
-}
-
-__device__ __forceinline__ float sp_first_lane(float x) {
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
-__device__ __forceinline__ double sp_first_lane(double x) {
-    const long long b = __double_as_longlong(x);
-    return __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                                (uint32_t)__builtin_amdgcn_readfirstlane((int)b));
-}
-
-__device__ __forceinline__ uint32_t sp_wave_max_u32(uint32_t x) {
-    x = max(x, (uint32_t)sp_dpp_i32<0xB1>((int)x));
-    x = max(x, (uint32_t)sp_dpp_i32<0x4E>((int)x));
-    x = max(x, (uint32_t)sp_dpp_i32<0x141>((int)x));
-    x = max(x, (uint32_t)sp_dpp_i32<0x140>((int)x));
-    return max(max((uint32_t)__builtin_amdgcn_readlane((int)x, 0), (uint32_t)__builtin_amdgcn_readlane((int)x, 16)),
-               max((uint32_t)__builtin_amdgcn_readlane((int)x, 32), (uint32_t)__builtin_amdgcn_readlane((int)x, 48)));
-}
+// ---- wave / workgroup reductions (mvm_wave.h; the 64-bit maximum is a shuffle loop) ----
 
 __device__ __forceinline__ long long sp_wave_max_i64(long long x) {
     for (int o = 1; o < 64; o <<= 1) {
@@ -716,7 +658,7 @@ __host__ __device__ inline size_t sp_solve_lds_bytes(int lw, int cap) {
 
 template <typename CT>
 __device__ __forceinline__ double sp_block_min(double x, double *s_red, int wave) {
-    x = sp_wave_min(x);
+    x = wave_min_f64(x);
     if ((threadIdx.x & 63) == 0) s_red[wave] = x;
     __syncthreads();
     const double r = fmin(fmin(s_red[0], s_red[1]), fmin(s_red[2], s_red[3]));
@@ -903,7 +845,7 @@ __global__ __launch_bounds__(kSpNT) __attribute__((amdgpu_waves_per_eu(KS == 1 ?
             if (k > 0) rd = load_row(i, na);
             const double ui = s_u[i];
             const int nl = __builtin_amdgcn_readfirstlane(rd.nl);
-            const CT th = sp_first_lane(rd.th);
+            const CT th = first_lane(rd.th);
             CT cv[KS];
 #pragma unroll
             for (int m = 0; m < KS; ++m) {
@@ -944,14 +886,14 @@ __global__ __launch_bounds__(kSpNT) __attribute__((amdgpu_waves_per_eu(KS == 1 ?
             }
             // wave records
             {
-                const double wa = sp_wave_min(ba);
+                const double wa = wave_min_f64(ba);
                 const bool el = bq >= 0 && ba == wa;
-                const int wpos = sp_wave_min_i32(el ? bpos : 0x7FFFFFFF);
+                const int wpos = wave_min_i32(el ? bpos : 0x7FFFFFFF);
                 const uint64_t win = __ballot(el && bpos == wpos);
                 const int wl = win ? (int)__builtin_ctzll(win) : 0;
                 const int wq = win ? __builtin_amdgcn_readlane(bq, wl) : -1;
                 const int wps = win ? __builtin_amdgcn_readlane(bps, wl) : -1;
-                const double wf = sp_wave_min(fr);
+                const double wf = wave_min_f64(fr);
                 const uint64_t fa = __ballot(fany);
                 const uint64_t tm = __ballot(tq >= 0);
                 const int wt = tm ? __builtin_amdgcn_readlane(tq, (int)__builtin_ctzll(tm)) : -1;
@@ -959,7 +901,7 @@ __global__ __launch_bounds__(kSpNT) __attribute__((amdgpu_waves_per_eu(KS == 1 ?
                 // (no column is moved yet in a search's first step)
                 uint32_t wk = 0;
                 if (k == 0)
-                    wk = sp_wave_max_u32(fany && fr == wf ? ((uint32_t)(L - 1 - lc) << 16) | (uint32_t)lc : 0u);
+                    wk = wave_max_u32(fany && fr == wf ? ((uint32_t)(L - 1 - lc) << 16) | (uint32_t)lc : 0u);
                 if (lane == 0) s_rec[par][wave] = SpRec{wa, wf, wpos, wq, wps, fa != 0, wt, wk};
             }
             __syncthreads();
@@ -1236,15 +1178,9 @@ int sp_launch(const LsapSparseArgs &a0, int32_t n, int64_t long_max, hipStream_t
     const int cap = a.s_cap;
     const int lw = (int)(((lmax + 63) / 64) * 2);            // even: the f64 arrays stay 8-aligned
     const size_t lds = sp_solve_lds_bytes(lw, cap);
-    const void *kern = cap <= kSpNT ? reinterpret_cast<const void *>(&sp_solve_kernel<CT, 1>)
-                                    : reinterpret_cast<const void *>(&sp_solve_kernel<CT, 4>);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
-    if (cap <= kSpNT)
-        sp_solve_kernel<CT, 1><<<dim3((unsigned)n), dim3(kSpNT), lds, s>>>(a, n, lw);
-    else
-        sp_solve_kernel<CT, 4><<<dim3((unsigned)n), dim3(kSpNT), lds, s>>>(a, n, lw);
+    void (*kern)(LsapSparseArgs, int32_t, int32_t) = cap <= kSpNT ? sp_solve_kernel<CT, 1> : sp_solve_kernel<CT, 4>;
+    if (const int st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return st;
+    kern<<<dim3((unsigned)n), dim3(kSpNT), lds, s>>>(a, n, lw);
     return mvm_check_launch("lsap_sparse");
 }
 
@@ -1278,24 +1214,13 @@ int64_t mvm_lsap_plan_resid(int32_t n_problems, const int64_t *rows, const int64
         mvm_set_error("mvm_lsap_plan_resid: invalid arguments");
         return -1;
     }
-    int64_t w = 0, o = 0;
-    for (int32_t p = 0; p < n_problems; ++p) {
-        if (rows[p] < 0 || cols[p] < 0 || rows[p] > 0x7FFFFFFF || cols[p] > 0x7FFFFFFF) {
-            mvm_set_error("mvm_lsap_plan_resid: problem dimensions out of range");
-            return -1;
-        }
-        ws_offs[p] = w;
-        out_offs[p] = o;
-        const bool tr = cols[p] < rows[p];
-        const int64_t nr = tr ? cols[p] : rows[p], nc = tr ? rows[p] : cols[p];
-        // only the candidate-list class's lists (no transposed cost: there is none)
-        if (rows[p] && cols[p] && nc <= kSpMaxCols && nr <= kSpMaxShort)
-            w += (int64_t)lsap_sparse_layout(nr, nc, sizeof(float), tr, true).total;
-        o += rows[p] < cols[p] ? rows[p] : cols[p];
-    }
-    ws_offs[n_problems] = w;
-    out_offs[n_problems] = o;
-    return w;
+    // only the candidate-list class's lists (no transposed cost: there is none)
+    const auto need = [](int64_t nr, int64_t nc, bool tr, size_t elem) {
+        if (nc > kSpMaxCols || nr > kSpMaxShort) return (int64_t)0;
+        return (int64_t)lsap_sparse_layout(nr, nc, elem, tr, true).total;
+    };
+    return mvm_lsap_plan_offsets("mvm_lsap_plan_resid", n_problems, rows, cols, sizeof(float), need,
+                                 ws_offs, out_offs);
 }
 
 int mvm_lsap_solve_resid(const int64_t *dims_dev, int32_t n_problems, const int64_t *ws_offs_dev,
@@ -1315,15 +1240,17 @@ int mvm_lsap_solve_resid(const int64_t *dims_dev, int32_t n_problems, const int6
                         (int)o.lsap_sparse_blocks);
     if (n_problems < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_problems");
     if (n_problems == 0) return MVM_OK;
+    // the null checks: what every call reads, then what the non-empty problems
+    // read (the 8-row minima are optional; refused after the bounds below)
     if (!dims_dev || !ws_offs_dev || !out_offs_dev || !status_dev)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
+    const bool data_null = (bmin8_dev && !bmin8_offs_dev) || !bm32_dev || !bm32_offs_dev || !segs_dev ||
+                           !resid_dev || !workspace_dev || !row_ind_dev || !col_ind_dev;
     if (max_n < 0 || max_n > kChunk)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "mvm_lsap_solve_resid: views of at most %d detections "
                         "(max_n %d)", kChunk, (int)max_n);
-    const int sp_lo = o.lsap_sparse_min_cols == 0 ? kSparseMinCols
-                                                  : (o.lsap_sparse_min_cols < 0 ? 0 : o.lsap_sparse_min_cols);
-    int wave_max = o.lsap_wave_max_cols == 0 ? 1024 : o.lsap_wave_max_cols;
-    wave_max = wave_max < 0 ? 0 : (wave_max > 1024 ? 1024 : wave_max);
+    const int sp_lo = mvm_resolve_limit(o.lsap_sparse_min_cols, kSparseMinCols, INT32_MAX);
+    const int wave_max = mvm_resolve_limit(o.lsap_wave_max_cols, kWaveMaxCols, kWaveMaxCols);
     if (long_max >= 1) {
         // there is no cost for any other class to read: every non-empty
         // problem must be the candidate-list class's (tall: P <= 256 < its long side)
@@ -1334,17 +1261,24 @@ int mvm_lsap_solve_resid(const int64_t *dims_dev, int32_t n_problems, const int6
                             "all of the candidate-list class (long sides >= %d, > %d, <= %d; short sides "
                             "<= %d)", (long long)long_min, (long long)long_max, (long long)short_max, sp_lo,
                             wave_max, kSpMaxCols, kSpMaxShort);
-        if ((bmin8_dev && !bmin8_offs_dev) || !bm32_dev || !bm32_offs_dev || !segs_dev || !resid_dev ||
-            !workspace_dev || !row_ind_dev || !col_ind_dev)   // (the 8-row minima are optional)
-            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
+        if (data_null) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
     }
     (void)workspace_bytes;   // the per-problem regions come from mvm_lsap_plan_resid's offsets
-    LsapSparseArgs sa{nullptr, nullptr, dims_dev, ws_offs_dev,
-                      reinterpret_cast<unsigned char *>(workspace_dev), out_offs_dev, row_ind_dev,
-                      col_ind_dev, status_dev, sp_lo > 0 ? sp_lo : 1, wave_max,
-                      (int32_t)(short_max < 1 ? 1 : short_max), bmin8_dev,
-                      bmin8_dev ? bmin8_offs_dev : nullptr, segs_dev,
-                      o.lsap_sparse_blocks ? o.lsap_sparse_blocks : kSpTB};
+    LsapSparseArgs sa{};     // no cost, no cost_offs
+    sa.dims = dims_dev;
+    sa.ws_offs = ws_offs_dev;
+    sa.ws = reinterpret_cast<unsigned char *>(workspace_dev);
+    sa.out_offs = out_offs_dev;
+    sa.row_ind = row_ind_dev;
+    sa.col_ind = col_ind_dev;
+    sa.status = status_dev;
+    sa.lo = sp_lo > 0 ? sp_lo : 1;
+    sa.wave_max = wave_max;
+    sa.s_cap = (int32_t)(short_max < 1 ? 1 : short_max);
+    sa.bmin8 = bmin8_dev;
+    sa.bmin8_offs = bmin8_dev ? bmin8_offs_dev : nullptr;
+    sa.segs = segs_dev;
+    sa.tb = o.lsap_sparse_blocks ? o.lsap_sparse_blocks : kSpTB;
     const int ld = (max_n + 3) / 4 * 4;
     sa.resid = resid_dev;
     sa.resid_ld = ld;

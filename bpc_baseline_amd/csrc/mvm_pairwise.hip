@@ -818,10 +818,7 @@ size_t pairwise_lds_bytes(int col_tile, int rows_per_wg, int row_slots, bool laz
 template <typename Kernel>
 int launch_lds(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                const PairArgs &a) {
-    if (lds > 65536 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return mvm_fail(MVM_ERR_HIP, "cannot raise the dynamic LDS limit to %zu bytes", lds);
+    if (const int st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(kern), lds)) return st;
     kern<<<grid, block, lds, stream>>>(a);
     return MVM_OK;
 }

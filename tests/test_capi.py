@@ -206,6 +206,34 @@ def test_lsap_plan_dtype(lib):
                                 o.ctypes.data) == -1
 
 
+def test_lsap_plan_offsets_pinned(lib):
+    """Every offset and the total of the three plans on one batch of shapes
+    (empty, square, wide, tall, each class's edge): recorded from the library
+    before the plan loops were merged into one."""
+    import numpy as np
+    shapes = [(0, 5), (5, 0), (3, 3), (24, 576), (576, 24), (1025, 4096), (256, 65536),
+              (65536, 256), (2000, 2000), (1, 70000)]
+    rows = np.array([s[0] for s in shapes], np.int64)
+    cols = np.array([s[1] for s in shapes], np.int64)
+    out_ref = [0, 0, 0, 3, 27, 51, 1076, 1332, 1588, 3588, 3589]
+    ws_ref = {
+        _native.MVM_F32: (74209024, [0, 0, 0, 4352, 31744, 112640, 265216, 2627072, 71838720,
+                                     71944448, 74185984]),
+        _native.MVM_F64: (143630336, [0, 0, 0, 5888, 47360, 195840, 348416, 4939520, 141260032,
+                                      141365760, 143607296]),
+        "resid": (584704, [0, 0, 0, 4096, 29696, 55296, 55296, 320000, 584704, 584704, 584704]),
+    }
+    for kind, (total_ref, offs_ref) in ws_ref.items():
+        ws, out = np.full(11, -7, np.int64), np.full(11, -7, np.int64)
+        if kind == "resid":
+            total = lib.mvm_lsap_plan_resid(10, rows.ctypes.data, cols.ctypes.data, ws.ctypes.data,
+                                            out.ctypes.data)
+        else:
+            total = lib.mvm_lsap_plan_ex(10, rows.ctypes.data, cols.ctypes.data, kind, ws.ctypes.data,
+                                         out.ctypes.data)
+        assert (total, ws.tolist(), out.tolist()) == (total_ref, offs_ref, out_ref), kind
+
+
 # ---- the cube-free association (ABI 7) ----------------------------------------
 def test_cube_free_class_bounds_and_scenes(lib):
     import numpy as np
