@@ -167,15 +167,17 @@ def match_objects(cost_matrix, threshold) -> List[Tuple[int, int, int]]:
 
     The assignment runs on the GPU and equals scipy ``linear_sum_assignment``
     on the ``(N*M, P)`` flattening, in the precision scipy uses for the
-    cube's dtype; strict ``<`` threshold on the cube's own values;
-    ``i = r // M``, ``j = r % M``.
+    cube's dtype; strict ``<`` threshold on the cube's own values, compared
+    in float64 as numpy 1.26 compares a float32 scalar with a Python number
+    (the contract of mvm_select_triangulate; NumPy >= 2 would round the
+    threshold to float32 first); ``i = r // M``, ``j = r % M``.
     """
     N, M, P = cost_matrix.shape
     flat = cost_matrix.reshape(N * M, P)
     rows, cols = linear_sum_assignment(flat)
     out = []
     for r, c in zip(rows, cols):
-        if flat[r, c] < threshold:
+        if float(flat[r, c]) < threshold:
             out.append((np.int64(r) // M, np.int64(r) % M, np.int64(c)))
     return out
 

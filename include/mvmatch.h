@@ -462,7 +462,10 @@ int mvm_triangulate_dlt(const double *proj_dev, const int32_t *set_of_point_dev,
  * s's assignment (row_ind/col_ind at lsap_out_offs_dev[s], the flattened
  * (N*M, P) cube at cube_offs_dev[s]) is filtered by cube value < threshold
  * (match_objects :111; compared in float64, as numpy 1.26 compares a float32
- * scalar with a Python number), decoded i = r / M, j = r % M, k = c
+ * scalar with a Python number: (double)value < threshold, so under threshold
+ * 0.7 a cost of float32(0.7) is kept; NaN on either side keeps nothing; the
+ * CPU restatements oracle/lsap.match_objects and oracle/pipeline.select_sort
+ * compare the same way under any NumPy), decoded i = r / M, j = r % M, k = c
  * (:112-114), stably sorted by cost (:183) and triangulated from the
  * centroids pts_dev (CSR cam_offs_dev, 3 views per scene) with the scene's
  * projection matrices proj_dev [S, 3, 3, 4] (K @ RT[:3], :86-94).  Match w

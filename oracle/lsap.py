@@ -98,8 +98,14 @@ def linear_sum_assignment(cost: np.ndarray):
 
 
 def match_objects(cost_matrix: np.ndarray, threshold):
-    """epipolar_matching.py:100-116 on top of the restated solver."""
+    """epipolar_matching.py:100-116 on top of the restated solver.
+
+    The threshold is compared in float64 (``float(flat[r, c]) < threshold``),
+    as numpy 1.26 compares a float32 scalar with a Python number: the contract
+    of include/mvmatch.h, stated explicitly because NumPy >= 2 (NEP 50) would
+    round the threshold to float32 first."""
     N, M, P = cost_matrix.shape
     flat = cost_matrix.reshape(N * M, P)
     rows, cols = linear_sum_assignment(flat)
-    return [(int(r) // M, int(r) % M, int(c)) for r, c in zip(rows, cols) if flat[r, c] < threshold]
+    return [(int(r) // M, int(r) % M, int(c)) for r, c in zip(rows, cols)
+            if float(flat[r, c]) < threshold]

@@ -1,9 +1,11 @@
 """CPU restatement of the steps either side of the matcher.
 
-TEST INFRASTRUCTURE ONLY: the checker for mvm_pack_detections and
-mvm_triangulate_dlt (bpc_baseline_amd/csrc/mvm_pipeline.hip).  Pinned against
+TEST INFRASTRUCTURE ONLY: the checker for mvm_pack_detections,
+mvm_triangulate_dlt and the threshold + sort of mvm_select_triangulate
+(bpc_baseline_amd/csrc/mvm_pipeline.hip).  Pinned against
 tests/golden/a8_detect.npz and a9_triangulate.npz, which hold the reference's
-own outputs (oracle/gen_golden.py).
+own outputs (oracle/gen_golden.py), and (select_sort) against
+oracle/lsap.match_objects on the a3 and a7 fixtures.
 """
 from __future__ import annotations
 
@@ -41,6 +43,33 @@ def detect_pack(boxes: np.ndarray, conf: np.ndarray, cls: np.ndarray, in_offs: n
     return (np.concatenate(bbox).reshape(-1, 4) if bbox else np.zeros((0, 4), np.int64),
             np.concatenate(center).reshape(-1, 2) if center else np.zeros((0, 2)),
             out_offs)
+
+
+def select_sort(cube_flat: np.ndarray, M: int, P: int, row_ind: np.ndarray, col_ind: np.ndarray,
+                threshold: float):
+    """The tail of PoseEstimator._match before triangulation
+    (process_pose.py:182-183 with match_objects, epipolar_matching.py:110-115):
+    the checker for mvm_select_triangulate's match and cost outputs.
+
+    Assignment m of the flattened (N*M, P) float32 cube is kept iff
+    ``float(np.float32(v_m)) < float(threshold)``: an explicit float64 compare,
+    the contract of include/mvmatch.h, whatever the installed NumPy would
+    promote a float32 scalar against a Python number to.  Kept entries are
+    decoded ``i = r // M, j = r % M, k = c`` and ordered by a stable sort of
+    their float32 costs (Python's sorted: ties keep the assignment's order).
+    -> (match int32 [k, 3], cost float32 [k]).
+    """
+    cube_flat = np.asarray(cube_flat, np.float32).reshape(-1)
+    r = np.asarray(row_ind, np.int64).reshape(-1)
+    c = np.asarray(col_ind, np.int64).reshape(-1)
+    if r.size == 0:
+        return np.zeros((0, 3), np.int32), np.zeros(0, np.float32)
+    v = cube_flat[r * P + c]
+    keep = v.astype(np.float64) < float(threshold)      # NaN on either side: dropped
+    r, c, v = r[keep], c[keep], v[keep]
+    order = np.argsort(v, kind="stable")
+    r, c = r[order], c[order]
+    return np.stack([r // M, r % M, c], axis=1).astype(np.int32).reshape(-1, 3), v[order]
 
 
 def triangulate(proj: np.ndarray, pts: np.ndarray) -> np.ndarray:
