@@ -163,6 +163,11 @@ SIGNATURES = {
         _vp, _i32, _vp, _vp, _vp, _vp,      # resid, max_n, cam_offs, lsap_out_offs, row_ind, col_ind
         _vp, _vp, _i32, ctypes.c_double,    # pts, proj, n_scenes, threshold
         _vp, _vp, _vp, _vp, _vp]),          # match, cost, X, count, stream
+    "mvm_compact_matches": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp,            # match, cost, X, count, seg_offs
+        _vp, _vp, _vp, _i32, _i32,          # pts, boxes, cam_offs, n_scenes, scene_base
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp,  # dense_offs, scene, match, cost, X, boxes, cent (out)
+        _vp]),                              # stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -333,9 +333,103 @@ __global__ __launch_bounds__(kSelThreads) void select_triangulate_kernel(
     if (t == 0) count[s] = s_kept;
 }
 
+// ------------------------------------------------- match table ----
+// The select kernels leave scene s's matches at lsap_offs[s] with slack rows
+// behind them, as per-view indices.  This copies them to dense rows
+// dense_offs[s] + w and resolves the indices against the packer's rows, so a
+// row stands on its own (mvm_compact_matches).  One wave per scene, lanes
+// stride over its matches: no LDS, no barrier.  VEC: boxes / pts rows and
+// their triples move as 16-byte accesses (every base 16-byte aligned).
+constexpr int kCompactThreads = 256;
+constexpr int kCompactScenes = kCompactThreads / 64;
+
+template <bool VEC>
+__global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
+    const int32_t *__restrict__ match, const float *__restrict__ cost, const double *__restrict__ X,
+    const int32_t *__restrict__ count, const int64_t *__restrict__ seg_offs,
+    const int64_t *__restrict__ dense_offs, const double *__restrict__ pts,
+    const int32_t *__restrict__ boxes, const int64_t *__restrict__ cam_offs, int32_t n_scenes,
+    int32_t scene_base, int32_t *__restrict__ scene_out, int32_t *__restrict__ match_out,
+    float *__restrict__ cost_out, double *__restrict__ X_out, int32_t *__restrict__ boxes_out,
+    double *__restrict__ cent_out) {
+    const int lane = threadIdx.x % 64;
+    const int64_t s = (int64_t)blockIdx.x * kCompactScenes + threadIdx.x / 64;
+    if (s >= n_scenes) return;
+    const int64_t src = seg_offs[s], dst = dense_offs[s];
+    const int32_t n = count[s];
+    const int64_t c[3] = {cam_offs[3 * s], cam_offs[3 * s + 1], cam_offs[3 * s + 2]};
+    for (int32_t w = lane; w < n; w += 64) {
+        const int64_t a = src + w, r = dst + w;
+        int32_t m[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) m[v] = match[3 * a + v];
+        scene_out[r] = scene_base + (int32_t)s;
+        cost_out[r] = cost[a];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            match_out[3 * r + v] = m[v];
+            X_out[3 * r + v] = X[3 * a + v];
+        }
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const int64_t row = c[v] + m[v], o = 3 * r + v;
+            if (VEC) {
+                reinterpret_cast<int4 *>(boxes_out)[o] = reinterpret_cast<const int4 *>(boxes)[row];
+                reinterpret_cast<double2 *>(cent_out)[o] = reinterpret_cast<const double2 *>(pts)[row];
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = boxes[4 * row + q];
+                cent_out[2 * o] = pts[2 * row];
+                cent_out[2 * o + 1] = pts[2 * row + 1];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const double *X_dev,
+                        const int32_t *count_dev, const int64_t *seg_offs_dev, const double *pts_dev,
+                        const int32_t *boxes_dev, const int64_t *cam_offs_dev, int32_t n_scenes,
+                        int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
+                        int32_t *match_out_dev, float *cost_out_dev, double *X_out_dev,
+                        int32_t *boxes_out_dev, double *cent_out_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    const struct {
+        const void *p;
+        const char *name;
+    } args[] = {{match_dev, "match_dev"},         {cost_dev, "cost_dev"},
+                {X_dev, "X_dev"},                 {count_dev, "count_dev"},
+                {seg_offs_dev, "seg_offs_dev"},   {pts_dev, "pts_dev"},
+                {boxes_dev, "boxes_dev"},         {cam_offs_dev, "cam_offs_dev"},
+                {dense_offs_dev, "dense_offs_dev"}, {scene_out_dev, "scene_out_dev"},
+                {match_out_dev, "match_out_dev"}, {cost_out_dev, "cost_out_dev"},
+                {X_out_dev, "X_out_dev"},         {boxes_out_dev, "boxes_out_dev"},
+                {cent_out_dev, "cent_out_dev"}};
+    for (const auto &a : args)
+        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
+    const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
+    const bool vec = ((reinterpret_cast<uintptr_t>(pts_dev) | reinterpret_cast<uintptr_t>(boxes_dev) |
+                       reinterpret_cast<uintptr_t>(boxes_out_dev) |
+                       reinterpret_cast<uintptr_t>(cent_out_dev)) & 15) == 0;
+    if (vec)
+        compact_matches_kernel<true><<<grid, kCompactThreads, 0, s>>>(
+            match_dev, cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev, boxes_dev,
+            cam_offs_dev, n_scenes, scene_base, scene_out_dev, match_out_dev, cost_out_dev, X_out_dev,
+            boxes_out_dev, cent_out_dev);
+    else
+        compact_matches_kernel<false><<<grid, kCompactThreads, 0, s>>>(
+            match_dev, cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev, boxes_dev,
+            cam_offs_dev, n_scenes, scene_base, scene_out_dev, match_out_dev, cost_out_dev, X_out_dev,
+            boxes_out_dev, cent_out_dev);
+    return mvm_check_launch("compact_matches_kernel");
+}
 
 int mvm_pack_detections(const float *boxes_dev, const float *conf_dev, const float *cls_dev,
                         const int64_t *img_offs_dev, int32_t n_img, float conf_thresh,

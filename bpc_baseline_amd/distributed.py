@@ -16,11 +16,13 @@ import datetime
 import os
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 __all__ = ["DistEnv", "init_from_env", "shard_range", "gather_rows", "max_over_ranks",
-           "sum_over_ranks", "ChunkedRowGather", "DEFAULT_TIMEOUT_S"]
+           "sum_over_ranks", "ChunkedRowGather", "DEFAULT_TIMEOUT_S", "gather_tables",
+           "match_captures_sharded"]
 
 # every collective (RCCL or gloo) of a process group made here fails after
 # this long instead of hanging the job: a stuck gather on an 8-GPU run ends
@@ -210,3 +212,94 @@ class ChunkedRowGather:
             dev.copy_(host)
         self.copy_back = []
         return self.recv
+
+
+def gather_tables(env: DistEnv, table, n_captures: int):
+    """Gather every rank's ``MatchTable`` (``inference.batch_match``) to rank 0.
+
+    Rank r holds the table of its ``n_captures`` captures -- a contiguous
+    range, in rank order -- with scene ids counted from 0 (``table()``'s
+    default).  One all_gather of (rows, captures) per rank sizes everything;
+    then the per-capture counts and each field are gathered to rank 0, padded
+    to the largest shard and trimmed there: over the default group when it is
+    RCCL, on host memory for gloo (as ``gather_rows``).  A field no rank has
+    a row of is not exchanged; every rank skips it alike, so a rank with no
+    rows or no captures still takes part in every collective.  Rank 0's scene
+    ids are renumbered by each rank's first global capture (the gathered
+    capture counts, in rank order) and ``offs`` is rebuilt from the gathered
+    counts.  -> the table of all captures on rank 0 (host tensors under gloo),
+    None elsewhere; ``table`` itself when no process group is initialised."""
+    from .inference.batch_match import MatchTable
+    counts = np.diff(np.asarray(table.offs, np.int64))
+    if counts.size != n_captures:
+        raise ValueError(f"table of {counts.size} captures, n_captures {n_captures}")
+    if not env.initialised:
+        return table
+    on_host = env.backend == "gloo"
+    dev = torch.device("cpu") if on_host else env.device
+    n_rows = int(table.scene.shape[0])
+    mine = torch.tensor([n_rows, n_captures], dtype=torch.int64, device=dev)
+    sizes = [torch.zeros_like(mine) for _ in range(env.world)]
+    dist.all_gather(sizes, mine)
+    sizes = torch.stack(sizes).cpu().numpy()
+    rows, caps = sizes[:, 0], sizes[:, 1]
+
+    def gather(t: torch.Tensor, lens: np.ndarray) -> Optional[torch.Tensor]:
+        # rows of t ([n, ...]) from every rank, n = lens[rank]
+        n_max = int(lens.max())
+        if n_max == 0:
+            return t.to(dev)[:0] if env.is_root else None
+        t = t.to(dev)
+        if t.shape[0] < n_max:
+            t = torch.cat([t, t.new_zeros((n_max - t.shape[0],) + tuple(t.shape[1:]))])
+        bufs = [torch.empty_like(t) for _ in range(env.world)] if env.is_root else None
+        dist.gather(t.contiguous(), gather_list=bufs, dst=0)
+        return torch.cat([b[:int(n)] for b, n in zip(bufs, lens)]) if env.is_root else None
+
+    got_counts = gather(torch.from_numpy(counts), caps)
+    fields = {k: gather(getattr(table, k), rows) for k in MatchTable.FIELDS}
+    if not env.is_root:
+        return None
+    first = np.concatenate([[0], np.cumsum(caps)[:-1]])       # each rank's first global capture
+    shift = torch.from_numpy(np.repeat(first, rows).astype(np.int32)).to(dev)
+    fields["scene"] = fields["scene"] + shift
+    offs = np.zeros(int(caps.sum()) + 1, np.int64)
+    np.cumsum(got_counts.cpu().numpy(), out=offs[1:])
+    return MatchTable(offs=offs, **fields)
+
+
+def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
+                           split: Optional[dict] = None, **kw):
+    """``match_captures`` with the captures sharded over the ranks: every rank
+    passes its own shard (a contiguous range of the captures, in rank order;
+    ``shard_range`` makes such ranges), runs the device chain on it -- not at
+    all when its shard is empty --, compacts the result into a ``MatchTable``
+    and the tables are gathered to rank 0 (``gather_tables``).  ``kw`` goes to
+    ``match_captures`` (``keep_cube``, the thresholds, ``F``, ``proj``, ...).
+    ``split``: a dict that receives this rank's seconds in "chain", "table"
+    and "gather" (synchronising after each, so only for measurements).
+    -> the ``MatchTable`` of all captures on rank 0, None elsewhere."""
+    import time
+    from .inference.batch_match import MatchTable, match_captures
+    dev = boxes.device
+    clock = [time.perf_counter()]
+
+    def mark(name):
+        if split is not None:
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            split[name] = split.get(name, 0.0) + now - clock[0]
+            clock[0] = now
+
+    n_img = int(img_offs.numel()) - 1
+    if n_img % 3:
+        raise ValueError("img_offs must describe 3 images per capture")
+    S = n_img // 3
+    batch = match_captures(boxes, conf, cls, img_offs, Ks, RTs, **kw) if S else None
+    mark("chain")
+    table = batch.table() if S else MatchTable.empty(dev)
+    mark("table")
+    out = gather_tables(env, table, S)
+    mark("gather")
+    return out

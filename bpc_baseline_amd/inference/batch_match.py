@@ -36,7 +36,7 @@ import torch
 from .. import ops
 from .utils.camera_utils import projection_matrices, rig_matrices
 
-__all__ = ["MatchBatch", "match_capture_stream", "match_captures", "projection_matrices",
+__all__ = ["MatchBatch", "MatchTable", "match_capture_stream", "match_captures", "projection_matrices",
            "rig_matrices", "rig_worker_pool"]
 
 
@@ -53,6 +53,11 @@ class MatchBatch:
     boxes: torch.Tensor          # int32 [n, 4]     packed int boxes
     cam_offs: np.ndarray         # int64 [3S + 1]   CSR of pts / boxes
     cube: Optional[torch.Tensor] = None
+    # what ``table`` hands the compaction kernel, kept on the device by
+    # match_captures (a batch built without them uploads the host copies)
+    offs_dev: Optional[torch.Tensor] = None       # int64 [S + 1]
+    count_dev: Optional[torch.Tensor] = None      # int32 [S]
+    cam_offs_dev: Optional[torch.Tensor] = None   # int64 [3S + 1]
 
     def host(self) -> dict:
         """One D2H copy of everything ``predictions`` reads."""
@@ -67,6 +72,69 @@ class MatchBatch:
         h = self.host()
         rows = self.cam_offs[3 * s:3 * s + 3][None, :] + h["match"][o:o + n].astype(np.int64)
         return [(h["boxes"][rows[q]], h["pts"][rows[q]], h["X"][o + q]) for q in range(n)]
+
+    def table(self, scene_base: int = 0) -> "MatchTable":
+        """The batch as a dense ``MatchTable`` (mvm_compact_matches): the
+        ``count.sum()`` matches in consecutive rows, each with its boxes and
+        centroids, scene ids starting at ``scene_base``.  No host sync: the
+        row count is ``count``, already on the host."""
+        S = int(self.count.size)
+        offs = np.zeros(S + 1, np.int64)
+        np.cumsum(self.count, out=offs[1:])
+        n = int(offs[-1])
+        dev = self.match.device
+        if n == 0:
+            return MatchTable.empty(dev, offs)
+        seg, cam, cnt = self.offs_dev, self.cam_offs_dev, self.count_dev
+        if seg is None or cam is None:
+            seg, cam = ops._h2d_int64([self.offs, self.cam_offs], dev)
+        if cnt is None:
+            cnt = torch.from_numpy(np.ascontiguousarray(self.count, np.int32)).to(dev)
+        _, scene, match, cost, X, boxes, cent = ops.compact_matches(
+            self.match, self.cost, self.X, cnt, seg, self.pts, self.boxes, cam, scene_base)
+        return MatchTable(scene=scene[:n], match=match[:n], cost=cost[:n], X=X[:n], boxes=boxes[:n],
+                          centroids=cent[:n], offs=offs)
+
+
+@dataclass
+class MatchTable:
+    """Matches of a batch as dense, self-contained rows (capture s owns rows
+    ``offs[s] : offs[s + 1]``, in _match's order): what ``MatchBatch`` holds
+    without its unused rows and with every index resolved, so a table can be
+    copied to the host in one piece or gathered from another rank
+    (``distributed.gather_tables``)."""
+    scene: torch.Tensor          # int32 [n]        capture id of the row
+    match: torch.Tensor          # int32 [n, 3]     (i, j, k)
+    cost: torch.Tensor           # float32 [n]
+    X: torch.Tensor              # float64 [n, 3]   triangulated centre (PosePrediction.t)
+    boxes: torch.Tensor          # int32 [n, 3, 4]  the three views' boxes
+    centroids: torch.Tensor      # float64 [n, 3, 2]
+    offs: np.ndarray             # int64 [S + 1]    host
+
+    FIELDS = ("scene", "match", "cost", "X", "boxes", "centroids")
+
+    @classmethod
+    def empty(cls, device, offs: Optional[np.ndarray] = None) -> "MatchTable":
+        """A table of no rows (``offs``: all zero, one entry per capture + 1;
+        default no captures)."""
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        return cls(scene=e(0, torch.int32), match=e((0, 3), torch.int32), cost=e(0, torch.float32),
+                   X=e((0, 3), torch.float64), boxes=e((0, 3, 4), torch.int32),
+                   centroids=e((0, 3, 2), torch.float64),
+                   offs=np.zeros(1, np.int64) if offs is None else offs)
+
+    def host(self) -> dict:
+        """One D2H copy of the n rows."""
+        if not hasattr(self, "_host"):
+            self._host = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        return self._host
+
+    def predictions(self, s: int) -> List[tuple]:
+        """Exactly ``MatchBatch.predictions(s)``: (boxes int32 [3, 4],
+        centroids f64 [3, 2], t f64 [3]) per match of capture s."""
+        h = self.host()
+        return [(h["boxes"][r], h["centroids"][r], h["X"][r])
+                for r in range(int(self.offs[s]), int(self.offs[s + 1]))]
 
 
 def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
@@ -141,7 +209,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
         # the cost) with it; each part is a contiguous sub-batch
         res = _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, float(matching_threshold), free,
                            mark)
-    match, cost, X, lstat, count, out_offs_host, cube = res
+    match, cost, X, lstat, count, out_offs_host, cube, out_offs = res
     # one device -> host copy: assignment statuses and match counts
     sc = torch.cat([lstat, count]).cpu().numpy()
     bad, count_h = sc[:S], sc[S:]
@@ -151,14 +219,16 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     mark("results D2H")
     return MatchBatch(match=match, cost=cost, X=X, count=count_h,
                       offs=out_offs_host, pts=pts, boxes=boxes_int, cam_offs=cam_offs_host,
-                      cube=cube if keep_cube else None)
+                      cube=cube if keep_cube else None, offs_dev=out_offs, count_dev=count,
+                      cam_offs_dev=cam_offs)
 
 
 def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, cube_free, keep_cube,
                   mark):
     """Cube (or, cube_free, its 8-row minima + pair residuals) -> assignment ->
     select/DLT of S scenes whose CSR offsets are ``cam_offs`` (device) /
-    ``cam_offs_host``.  -> (match, cost, X, status, count, out_offs_host, cube or None)."""
+    ``cam_offs_host``.  -> (match, cost, X, status, count, out_offs_host, cube or None,
+    out_offs on the device)."""
     dev = pts.device
     plan = ops.TripletPlan(cam_offs_host, S, device=dev)
     c3 = plan.counts
@@ -177,7 +247,7 @@ def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, c
         match, cost, X, count = ops.select_triangulate_resid(plan, cam_offs, lplan.out_offs, row_ind,
                                                              col_ind, pts, proj_dev, threshold)
         mark("select")
-        return match, cost, X, lstat, count, lplan.out_offs_host, None
+        return match, cost, X, lstat, count, lplan.out_offs_host, None, lplan.out_offs
     # flattened cubes of the candidate-list class: the cube kernel also writes
     # the 8-row minima that class reduces
     bm8 = None
@@ -196,7 +266,8 @@ def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, c
     match, cost, X, count = ops.select_triangulate(cube, plan.cube_offs, cam_offs, lplan.out_offs,
                                                    row_ind, col_ind, pts, proj_dev, threshold)
     mark("select")
-    return match, cost, X, lstat, count, lplan.out_offs_host, (cube if keep_cube else None)
+    return (match, cost, X, lstat, count, lplan.out_offs_host, (cube if keep_cube else None),
+            lplan.out_offs)
 
 
 def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
@@ -227,17 +298,19 @@ def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
              np.concatenate([np.arange(out_offs[s], out_offs[s] + caps[s]) for s in part]).astype(np.int64),
              np.arange(int(caps[part].sum()), dtype=np.int64), sub_co], dev)
         sub_pts = pts.index_select(0, sel) if rows.size else pts[:0]
-        m, c, x, st, n, _, _ = _device_chain(sub_pts, sub_co_dev, sub_co,
-                                             F3.index_select(0, idx).reshape(-1),
-                                             proj_dev.index_select(0, idx), part.size, threshold,
-                                             bool(free[part[0]]), False, mark)
+        m, c, x, st, n = _device_chain(sub_pts, sub_co_dev, sub_co,
+                                       F3.index_select(0, idx).reshape(-1),
+                                       proj_dev.index_select(0, idx), part.size, threshold,
+                                       bool(free[part[0]]), False, mark)[:5]
         if src_rows.numel():
             match.index_copy_(0, dst_rows, m.index_select(0, src_rows))
             cost.index_copy_(0, dst_rows, c.index_select(0, src_rows))
             X.index_copy_(0, dst_rows, x.index_select(0, src_rows))
         status.index_copy_(0, idx, st)
         count.index_copy_(0, idx, n)
-    return match[:cap], cost[:cap], X[:cap], status, count, out_offs, None
+    # the merged layout's offsets, for MatchBatch.table: uploaded once
+    out_offs_dev, = ops._h2d_int64([out_offs], dev)
+    return match[:cap], cost[:cap], X[:cap], status, count, out_offs, None, out_offs_dev
 
 
 def _rig_inputs(batch: Sequence):

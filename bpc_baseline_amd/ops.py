@@ -36,7 +36,7 @@ __all__ = [
     "hbm_write_probe", "LsapPlan", "linear_sum_assignment_batched",
     "pack_detections", "triangulate_dlt", "select_triangulate",
     "triplet_minima", "linear_sum_assignment_resid", "select_triangulate_resid",
-    "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats",
+    "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats", "compact_matches",
 ]
 
 
@@ -474,6 +474,54 @@ def _(resid, max_n, cam_offs, lsap_offs, row_ind, col_ind, pts, proj, threshold,
     return None
 
 
+@torch.library.custom_op("mvmatch::compact_matches_out",
+                         mutates_args=("dense_offs", "scene_out", "match_out", "cost_out", "X_out",
+                                       "boxes_out", "cent_out"))
+def compact_matches_out(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_offs: Tensor,
+                        pts: Tensor, boxes: Tensor, cam_offs: Tensor, scene_base: int,
+                        dense_offs: Tensor, scene_out: Tensor, match_out: Tensor, cost_out: Tensor,
+                        X_out: Tensor, boxes_out: Tensor, cent_out: Tensor) -> None:
+    """The select kernels' matches as dense, self-contained rows
+    (mvm_compact_matches, ABI 8).  Outputs hold ``match.shape[0]`` rows."""
+    dev = match.device
+    if dev.type != "cuda":
+        raise ValueError("match must be a GPU tensor (the table has no CPU path)")
+    n_scenes = count.numel()
+    cap = int(match.shape[0]) if match.dim() == 2 else -1
+    if match.dim() != 2 or match.shape[1] != 3:
+        raise ValueError("match must be [cap, 3]")
+    for t, name, dt, numel in ((match, "match", torch.int32, 3 * cap), (cost, "cost", torch.float32, cap),
+                               (X, "X", torch.float64, 3 * cap), (count, "count", torch.int32, n_scenes),
+                               (seg_offs, "seg_offs", torch.int64, n_scenes + 1),
+                               (pts, "pts", torch.float64, 0), (boxes, "boxes", torch.int32, 0),
+                               (cam_offs, "cam_offs", torch.int64, 3 * n_scenes + 1),
+                               (dense_offs, "dense_offs", torch.int64, n_scenes + 1),
+                               (scene_out, "scene_out", torch.int32, cap),
+                               (match_out, "match_out", torch.int32, 3 * cap),
+                               (cost_out, "cost_out", torch.float32, cap),
+                               (X_out, "X_out", torch.float64, 3 * cap),
+                               (boxes_out, "boxes_out", torch.int32, 12 * cap),
+                               (cent_out, "cent_out", torch.float64, 6 * cap)):
+        _require(t, name, dt, dev)
+        if numel and t.numel() != numel and name in ("seg_offs", "cam_offs", "dense_offs"):
+            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+        if t.numel() < numel:
+            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
+    if boxes.numel() != 2 * pts.numel():
+        raise ValueError("pts [n, 2] and boxes [n, 4] differ in rows")
+    st = _native.load().mvm_compact_matches(
+        _p(match), _p(cost), _p(X), _p(count), _p(seg_offs), _p(pts), _p(boxes), _p(cam_offs),
+        n_scenes, int(scene_base), _p(dense_offs), _p(scene_out), _p(match_out), _p(cost_out),
+        _p(X_out), _p(boxes_out), _p(cent_out), _stream(match))
+    _native.check("mvm_compact_matches", st)
+
+
+@compact_matches_out.register_fake
+def _(match, cost, X, count, seg_offs, pts, boxes, cam_offs, scene_base, dense_offs, scene_out,
+      match_out, cost_out, X_out, boxes_out, cent_out):
+    return None
+
+
 # ---------------------------------------------------------------- plans ----
 class PairwisePlan:
     """Offsets of every (scene, pair) residual matrix and argmin row block.
@@ -892,3 +940,33 @@ def select_triangulate_resid(tplan: TripletPlan, cam_offs: Tensor, lsap_offs: Te
                                                    row_ind, col_ind, pts, proj.contiguous(),
                                                    float(threshold), match, cost, X, count)
     return match, cost, X, count
+
+
+def compact_matches(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_offs: Tensor,
+                    pts: Tensor, boxes: Tensor, cam_offs: Tensor, scene_base: int = 0):
+    """The dense match table of a select_triangulate(_resid) result (device):
+    scene s's ``count[s]`` matches, found at rows ``seg_offs[s]`` of match /
+    cost / X, copied to rows ``dense_offs[s]`` with their boxes and centroids
+    gathered from the packer's ``boxes`` / ``pts`` (CSR ``cam_offs``).
+    -> (dense_offs i64 [S+1], scene i32 [cap], match i32 [cap, 3], cost f32 [cap],
+    X f64 [cap, 3], boxes i32 [cap, 3, 4], centroids f64 [cap, 3, 2]); rows
+    at and beyond ``dense_offs[S]`` (= count.sum()) are unused capacity."""
+    dev = match.device
+    cap = int(match.shape[0])
+    n_scenes = int(count.numel())
+    dense_offs = torch.zeros(n_scenes + 1, dtype=torch.int64, device=dev)
+    rows = max(cap, 1)
+    scene = torch.empty(rows, dtype=torch.int32, device=dev)
+    match_out = torch.empty((rows, 3), dtype=torch.int32, device=dev)
+    cost_out = torch.empty(rows, dtype=torch.float32, device=dev)
+    X_out = torch.empty((rows, 3), dtype=torch.float64, device=dev)
+    boxes_out = torch.empty((rows, 3, 4), dtype=torch.int32, device=dev)
+    cent_out = torch.empty((rows, 3, 2), dtype=torch.float64, device=dev)
+    # no row to copy (no capacity, or no detection a match could name): every
+    # count is 0 and the offsets stay 0; nothing is launched
+    if n_scenes and cap and pts.numel():
+        torch.ops.mvmatch.compact_matches_out(match, cost, X, count, seg_offs, pts, boxes, cam_offs,
+                                              int(scene_base), dense_offs, scene, match_out, cost_out,
+                                              X_out, boxes_out, cent_out)
+    return (dense_offs, scene[:cap], match_out[:cap], cost_out[:cap], X_out[:cap], boxes_out[:cap],
+            cent_out[:cap])

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MVM_ABI_VERSION 7
+#define MVM_ABI_VERSION 8
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -487,6 +487,36 @@ int mvm_select_triangulate_resid(const double *resid_dev, int32_t max_n, const i
                                  const double *proj_dev, int32_t n_scenes, double threshold,
                                  int32_t *match_dev, float *cost_dev, double *X_dev, int32_t *count_dev,
                                  mvm_stream_t stream);
+
+/*
+ * The dense match table (ABI 8): the matches the select kernels left at
+ * seg_offs_dev[s] (the lsap_out_offs_dev they were given), with unused rows
+ * behind each scene and as per-view indices, copied to consecutive rows that
+ * stand on their own -- what PosePrediction holds (process_pose.py:79-94:
+ * boxes, centroids, t) plus the scene id, so a table can leave the device
+ * or the rank that made it.  Inputs (read only, not aliasing the outputs):
+ * match_dev int32 [cap, 3], cost_dev f32 [cap], X_dev f64 [cap, 3],
+ * count_dev int32 [S] as mvm_select_triangulate(_resid) wrote them under
+ * seg_offs_dev int64 [S+1]; pts_dev f64 [n, 2], boxes_dev int32 [n, 4],
+ * cam_offs_dev int64 [3S+1] as mvm_pack_detections wrote them.
+ * Precondition: 0 <= count[s] <= seg_offs[s+1] - seg_offs[s] (true of
+ * everything the select kernels produce; not checked).
+ * Outputs, each with room for seg_offs[S] rows: dense_offs_dev int64 [S+1] =
+ * the exclusive prefix sum of count; for match w of scene s, at row
+ * r = dense_offs[s] + w: scene_out_dev[r] = scene_base + s (int32),
+ * match_out_dev[r] = (i, j, k) (int32 [3]), cost_out_dev[r] (f32),
+ * X_out_dev[r] (f64 [3]), boxes_out_dev[r] = boxes[cam_offs[3s+c] + idx_c],
+ * c = 0..2 (int32 [3, 4]) and cent_out_dev[r] = the same rows of pts
+ * (f64 [3, 2]).  Every value is a copy (bit-exact); rows at and beyond
+ * dense_offs[S] are not written.  Two launches (the prefix sum, the copy);
+ * n_scenes == 0 launches nothing.
+ */
+int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const double *X_dev,
+                        const int32_t *count_dev, const int64_t *seg_offs_dev, const double *pts_dev,
+                        const int32_t *boxes_dev, const int64_t *cam_offs_dev, int32_t n_scenes,
+                        int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
+                        int32_t *match_out_dev, float *cost_out_dev, double *X_out_dev,
+                        int32_t *boxes_out_dev, double *cent_out_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

@@ -27,6 +27,9 @@
 #                                             size (tools/ab_bmin8_input.py)
 #   bash tools/gpu.sh cubefree [bench args]  the cube-free association's suites, the
 #                                             c2match line without / with the cube, its trace
+#   bash tools/gpu.sh sharded [tool args]     match_captures_sharded: captures/s, each rank's
+#                                             chain / table / gather split, the match table
+#                                             against MatchBatch.host() (tools/bench_sharded_match.py)
 #   AB_LIBS="a.so b.so" bash tools/gpu.sh ab CMD...
 #                                             in-tree library builds (MVM_LIB_PATH) timed by
 #                                             CMD in alternating processes, AB_ROUNDS rounds
@@ -221,6 +224,11 @@ cubepin)
       echo "pmc $L $D^3 ok"
     done
   done ;;
+sharded)
+  # rank-sharded capture matching at one rank (N ranks: the same tool under torchrun)
+  timeout -k 10 "$LIMIT" python -u tools/bench_sharded_match.py "$@" > "$O/sharded_match.json" \
+    2> "$O/sharded_match.err" || fail "bench_sharded_match" "$O/sharded_match.err"
+  tail -1 "$O/sharded_match.json" ;;
 ab)
   for rnd in $(seq 1 "${AB_ROUNDS:-3}"); do
     for lib in $AB_LIBS; do
