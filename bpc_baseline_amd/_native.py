@@ -168,6 +168,10 @@ SIGNATURES = {
         _vp, _vp, _vp, _i32, _i32,          # pts, boxes, cam_offs, n_scenes, scene_base
         _vp, _vp, _vp, _vp, _vp, _vp, _vp,  # dense_offs, scene, match, cost, X, boxes, cent (out)
         _vp]),                              # stream
+    "mvm_rig_matrices": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp,                 # K, RT, pair_a (host), pair_b (host)
+        _i32, _i32, _i32,                   # n_scenes, n_cams, n_pairs
+        _vp, _vp, _vp, _vp]),               # F, proj (may be NULL), status, stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -14,6 +14,9 @@
 //    singular value, returned as X[:3] / X[3].  One-sided Jacobi SVD in fp64,
 //    one thread per point (tolerance parity with LAPACK's gesdd: the vector
 //    is unique up to sign, which X[:3]/X[3] cancels).
+//  * mvm_rig_matrices: compute_fundamental_matrix (camera_utils.py:23-46) per
+//    (capture, pair) and P = K @ RT[:3] (process_pose.py:91) per (capture,
+//    camera) for pinhole K, so a batch whose rigs differ needs no host numpy.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -386,9 +389,185 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
     }
 }
 
+// ------------------------------------------------- rig matrices ----
+// compute_fundamental_matrix (camera_utils.py:23-46) for every (capture, pair)
+// and P = K @ RT[:3] (process_pose.py:91) for every (capture, camera): one
+// work item each over a flat index, no LDS, no barrier.  The arithmetic is the
+// host function's, dtype by dtype, every dot product in index order.  As in
+// mvm_device.h, FMAs stand exactly where numpy / OpenBLAS placed them in the
+// reference run and nowhere else (this file's `#pragma clang fp contract(off)`
+// and the build's -ffp-contract=off): the fp64 3x3 products of F go through
+// OpenBLAS's FMA kernels, a0 * b0 then one fma per further term (dot3_fma: the
+// reference's own F of tests/golden/a6_fundamental.npz bit for bit); the
+// float32 inverse and P = K @ RT[:3] (numpy's own loop) are un-fused (dot3).
+constexpr int kRigThreads = 256;
+
+struct RigPairs {
+    int32_t a[MVM_MAX_PAIRS];
+    int32_t b[MVM_MAX_PAIRS];
+};
+
+__device__ __forceinline__ double dot3(double a0, double b0, double a1, double b1, double a2,
+                                       double b2) {
+    return (a0 * b0 + a1 * b1) + a2 * b2;
+}
+
+__device__ __forceinline__ double dot3_fma(double a0, double b0, double a1, double b1, double a2,
+                                           double b2) {
+    return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
+}
+
+// the K the kernel inverts: upper triangular without skew, K[2][2] == 1
+__device__ __forceinline__ bool pinhole_k(const float *K) {
+    return K[3] == 0.0f && K[6] == 0.0f && K[7] == 0.0f && K[1] == 0.0f && K[8] == 1.0f &&
+           K[0] != 0.0f && K[4] != 0.0f;
+}
+
+// float32 inverse of a pinhole K, column by column by back substitution,
+// x[r] = (b[r] - sum_{q > r} K[r][q] * x[q]) / K[r][r]: the bits of
+// np.linalg.inv (:38-39) for such K.  Promoted to fp64 as the product does.
+__device__ __forceinline__ void pinhole_inverse(const float *K, double inv[9]) {
+    float k[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) k[q] = K[q];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float x[3];
+#pragma unroll
+        for (int r = 2; r >= 0; --r) {
+            float acc = (r == c) ? 1.0f : 0.0f;
+#pragma unroll
+            for (int q = r + 1; q < 3; ++q) acc = acc - k[3 * r + q] * x[q];
+            x[r] = acc / k[3 * r + r];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) inv[3 * r + c] = (double)x[r];
+    }
+}
+
+__device__ __forceinline__ void rig_fundamental(const float *K1, const double *RT1, const float *K2,
+                                                const double *RT2, double *F) {
+    double R1[9], R2[9], t1[3], t2[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            R1[3 * i + j] = RT1[4 * i + j];
+            R2[3 * i + j] = RT2[4 * i + j];
+        }
+        t1[i] = RT1[4 * i + 3];
+        t2[i] = RT2[4 * i + 3];
+    }
+    double R[9], t[3];                       // R_rel = R2 R1^T (:27), t_rel = t2 - R_rel t1 (:28)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            R[3 * i + j] = dot3_fma(R2[3 * i], R1[3 * j], R2[3 * i + 1], R1[3 * j + 1], R2[3 * i + 2],
+                                R1[3 * j + 2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        t[i] = t2[i] - dot3_fma(R[3 * i], t1[0], R[3 * i + 1], t1[1], R[3 * i + 2], t1[2]);
+    // the skew matrix is float32 (:31-35) and promoted by the product (:37)
+    const double tx = (double)(float)t[0], ty = (double)(float)t[1], tz = (double)(float)t[2];
+    const double sk[9] = {0.0, -tz, ty, tz, 0.0, -tx, -ty, tx, 0.0};
+    double E[9], K1i[9], K2i[9], M[9], f[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            E[3 * i + j] = dot3_fma(sk[3 * i], R[j], sk[3 * i + 1], R[3 + j], sk[3 * i + 2], R[6 + j]);
+    pinhole_inverse(K1, K1i);
+    pinhole_inverse(K2, K2i);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)              // (K2inv^T E) K1inv, left to right (:40)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            M[3 * i + j] = dot3_fma(K2i[i], E[j], K2i[3 + i], E[3 + j], K2i[6 + i], E[6 + j]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            f[3 * i + j] = dot3_fma(M[3 * i], K1i[j], M[3 * i + 1], K1i[3 + j], M[3 * i + 2], K1i[6 + j]);
+    const double f22 = f[8];
+    const bool norm = fabs(f22) > 1e-8;      // :43-44
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = norm ? f[q] / f22 : f[q];
+}
+
+__global__ __launch_bounds__(kRigThreads) void rig_matrices_kernel(
+    const float *__restrict__ K, const double *__restrict__ RT, RigPairs pairs, int64_t n_items,
+    int32_t n_cams, int32_t n_pairs, int32_t per_scene, double *__restrict__ F,
+    double *__restrict__ proj, int32_t *__restrict__ status) {
+    const int64_t idx = (int64_t)blockIdx.x * kRigThreads + threadIdx.x;
+    if (idx >= n_items) return;
+    const int64_t s = idx / per_scene;
+    const int w = (int)(idx - s * per_scene);
+    const float *Ks = K + s * n_cams * 9;
+    const double *RTs = RT + s * n_cams * 16;
+    // every item of the capture reads all its K's, so they agree on the status
+    bool ok = true;
+    for (int c = 0; c < n_cams; ++c) ok &= pinhole_k(Ks + 9 * c);
+    if (w == 0) status[s] = ok ? 0 : 1;
+    if (!ok) return;                         // the caller fills this capture's rows
+    if (w < n_pairs) {
+        const int a = pairs.a[w], b = pairs.b[w];
+        rig_fundamental(Ks + 9 * a, RTs + 16 * a, Ks + 9 * b, RTs + 16 * b,
+                        F + (s * n_pairs + w) * 9);
+    } else {
+        const int c = w - n_pairs;           // P = K @ RT[:3]: float32 K promoted (process_pose.py:91)
+        const float *k = Ks + 9 * c;
+        const double *rt = RTs + 16 * c;
+        double *P = proj + (s * n_cams + c) * 12;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                P[4 * i + j] = dot3((double)k[3 * i], rt[j], (double)k[3 * i + 1], rt[4 + j],
+                                    (double)k[3 * i + 2], rt[8 + j]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int mvm_rig_matrices(const float *K_dev, const double *RT_dev, const int32_t *pair_a,
+                     const int32_t *pair_b, int32_t n_scenes, int32_t n_cams, int32_t n_pairs,
+                     double *F_dev, double *proj_dev, int32_t *status_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    if (n_cams < 2 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [2, %d]", n_cams, MVM_MAX_CAMS);
+    if (n_pairs < 1 || n_pairs > MVM_MAX_PAIRS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_pairs=%d outside [1, %d]", n_pairs, MVM_MAX_PAIRS);
+    const struct {
+        const void *p;
+        const char *name;
+    } args[] = {{K_dev, "K_dev"},   {RT_dev, "RT_dev"}, {pair_a, "pair_a"},
+                {pair_b, "pair_b"}, {F_dev, "F_dev"},   {status_dev, "status_dev"}};
+    for (const auto &a : args)
+        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    RigPairs pairs{};
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_a[p] < 0 || pair_a[p] >= n_cams || pair_b[p] < 0 || pair_b[p] >= n_cams ||
+            pair_a[p] == pair_b[p])
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "pair %d = (%d, %d) invalid for %d cameras", p,
+                            pair_a[p], pair_b[p], n_cams);
+        pairs.a[p] = pair_a[p];
+        pairs.b[p] = pair_b[p];
+    }
+    const int32_t per_scene = n_pairs + (proj_dev ? n_cams : 0);
+    const int64_t n_items = (int64_t)n_scenes * per_scene;
+    const int64_t grid = (n_items + kRigThreads - 1) / kRigThreads;
+    if (grid > kMaxGridBlocks)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more work items than one launch holds",
+                        n_scenes);
+    rig_matrices_kernel<<<(unsigned)grid, kRigThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        K_dev, RT_dev, pairs, n_items, n_cams, n_pairs, per_scene, F_dev, proj_dev, status_dev);
+    return mvm_check_launch("rig_matrices_kernel");
+}
 
 int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const double *X_dev,
                         const int32_t *count_dev, const int64_t *seg_offs_dev, const double *pts_dev,

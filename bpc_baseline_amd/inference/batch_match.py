@@ -10,6 +10,7 @@ with every O(n) and larger step on the GPU:
   1. mvm_pack_detections      boxes/conf/cls -> half-integer centroids (CSR)
   2. host                     F (batched, bit-equal to compute_fundamental_matrix)
                               and P = K @ RT[:3]; O(1) per capture
+     or mvm_rig_matrices      (rig="device") the same on the device, one launch
   3. mvm_triplet_cost_argmin  the (N, M, P) cube of every capture (+ its 8-row
                               minima when an assignment is large: _bmin8)
   4. mvm_lsap_solve           scipy-identical assignment of every flattened cube
@@ -34,7 +35,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .utils.camera_utils import projection_matrices, rig_matrices
+from .utils.camera_utils import pinhole_intrinsics, projection_matrices, rig_matrices
 
 __all__ = ["MatchBatch", "MatchTable", "match_capture_stream", "match_captures", "projection_matrices",
            "rig_matrices", "rig_worker_pool"]
@@ -142,7 +143,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    conf_thresh: float = 0.1, matching_threshold: float = 30,
                    keep_cube: bool = False, timings: Optional[dict] = None,
                    F: Optional[torch.Tensor] = None,
-                   proj: Optional[torch.Tensor] = None) -> MatchBatch:
+                   proj: Optional[torch.Tensor] = None, rig: str = "host") -> MatchBatch:
     """Detect-packing + matching + triangulation of S 3-camera captures.
 
     ``boxes`` f32 [n, 4] xyxy, ``conf``/``cls`` f32 [n]: the detector outputs
@@ -155,7 +156,24 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     may be passed as device tensors when the rigs repeat across batches (a
     static camera rig): they are then not recomputed on the host.  They must
     be what ``fundamental_matrices_batched`` / ``projection_matrices`` return.
+
+    ``rig`` says where F and proj are computed when they are not passed:
+    ``"host"`` (the default) by ``rig_matrices`` in numpy; ``"device"`` by
+    ``ops.rig_matrices`` (mvm_rig_matrices: no per-capture host work; F and proj
+    bit-equal to the host's where numpy's BLAS uses FMA kernels, F within a
+    few 1e-14 relative elsewhere),
+    with ``Ks`` / ``RTs`` as host arrays or device tensors; ``"auto"``
+    ``"device"`` when every K has the pinhole form the kernel inverts
+    (``pinhole_intrinsics``; device tensors are not inspected and go to the
+    device), else ``"host"``.  Under ``"device"`` a capture with another K is
+    computed on the host when ``Ks`` / ``RTs`` are host arrays, and raises
+    ``ValueError`` when they are device tensors.  ``F`` / ``proj`` cannot be
+    combined with ``rig="device"`` or ``"auto"``.
     """
+    if rig not in ("host", "device", "auto"):
+        raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
+    if rig != "host" and (F is not None or proj is not None):
+        raise TypeError(f"F / proj cannot be passed with rig={rig!r}: that path computes them")
     dev = boxes.device
     import time
     clock = [time.perf_counter()]
@@ -171,26 +189,53 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     if n_img % 3:
         raise ValueError("img_offs must describe 3 images per capture")
     S = n_img // 3
-    Ks = np.asarray(Ks, dtype=np.float32).reshape(S, 3, 3, 3)
-    RTs = np.asarray(RTs, dtype=np.float64).reshape(S, 3, 4, 4)
+    on_device = isinstance(Ks, torch.Tensor) or isinstance(RTs, torch.Tensor)
+    if rig == "host" or not on_device:
+        Ks = np.asarray(Ks, dtype=np.float32).reshape(S, 3, 3, 3)
+        RTs = np.asarray(RTs, dtype=np.float64).reshape(S, 3, 4, 4)
+    else:
+        Ks, RTs = Ks.reshape(S, 3, 3, 3), RTs.reshape(S, 3, 4, 4)
+    if rig == "auto":
+        rig = "device" if on_device or bool(pinhole_intrinsics(Ks).all()) else "host"
 
     pts, cam_offs, boxes_int, counts, status = ops.pack_detections(boxes, conf, cls, img_offs,
                                                                    conf_thresh)
     mark("pack")
-    # host work while the packing runs: F and P for every capture (once per
-    # distinct rig)
-    if F is None or proj is None:
-        F_h, P_h = rig_matrices(Ks, RTs)
-        if F is None:
-            F = torch.from_numpy(F_h).to(dev)
-        if proj is None:
-            proj = torch.from_numpy(P_h).to(dev)
+    rig_status = None
+    if rig == "device":
+        # F and P of every capture by one launch behind the packing; its
+        # per-capture status rides on the count copy below (no extra sync)
+        F, proj, rig_status = ops.rig_matrices(Ks, RTs, device=dev)
+        mark("F+P device")
+    else:
+        # host work while the packing runs: F and P for every capture (once per
+        # distinct rig)
+        if F is None or proj is None:
+            F_h, P_h = rig_matrices(Ks, RTs)
+            if F is None:
+                F = torch.from_numpy(F_h).to(dev)
+            if proj is None:
+                proj = torch.from_numpy(P_h).to(dev)
+        mark("F+P host")
     F_dev = F.reshape(-1)
     proj_dev = proj
-    mark("F+P host")
 
-    # one device -> host copy: the kept counts and the packing status
-    ch = torch.cat([counts, status]).cpu().numpy().astype(np.int64)
+    # one device -> host copy: the kept counts and the packing status (and the
+    # device rig's per-capture status)
+    ch = torch.cat([counts, status] + ([rig_status] if rig_status is not None else []))
+    ch = ch.cpu().numpy().astype(np.int64)
+    if rig_status is not None:
+        ch, rig_bad = ch[:n_img + 1], np.nonzero(ch[n_img + 1:])[0]
+        if rig_bad.size and on_device:
+            raise ValueError(f"captures {rig_bad[:8].tolist()} have a K outside the pinhole form "
+                             "mvm_rig_matrices inverts; pass Ks / RTs as host arrays (those captures "
+                             "are then computed on the host) or use rig='host'")
+        if rig_bad.size:
+            # the kernel left those captures' rows unwritten: the host's values
+            F_h, P_h = rig_matrices(Ks[rig_bad], RTs[rig_bad])
+            idx, = ops._h2d_int64([rig_bad], dev)
+            F.view(S, 27).index_copy_(0, idx, torch.from_numpy(F_h.reshape(-1, 27)).to(dev))
+            proj.index_copy_(0, idx, torch.from_numpy(P_h).to(dev))
     counts_host = ch[:-1]
     if ch[-1] != 0:
         raise ValueError("detector box with a non-finite or out-of-range coordinate")
@@ -357,7 +402,7 @@ def rig_worker_pool(n: int):
     return pool
 
 
-def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3,
+def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3, rig: str = "host",
                          **kwargs) -> Iterator[MatchBatch]:
     """``match_captures`` over a sequence of batches, pipelined: the host F and
     P of batch b+1 (``rig_matrices``: numpy, the same function, so the same
@@ -368,9 +413,19 @@ def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3,
     ``(boxes, conf, cls, img_offs, Ks, RTs)`` as ``match_captures`` takes them;
     ``kwargs`` are passed through (``F`` / ``proj`` are computed here).
     Results equal ``match_captures`` on each batch.
+
+    ``rig="device"`` / ``"auto"`` (``match_captures``' keyword): every batch
+    is ``match_captures(..., rig=rig)``; there is no host F / P to overlap, so
+    no worker pool is started or used (``rig_workers`` is ignored).
     """
     if "F" in kwargs or "proj" in kwargs:
         raise TypeError("match_capture_stream computes F and proj itself")
+    if rig not in ("host", "device", "auto"):
+        raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
+    if rig != "host":
+        for cur in batches:
+            yield match_captures(*cur, rig=rig, **kwargs)
+        return
     it = iter(batches)
     cur = next(it, None)
     if cur is None:

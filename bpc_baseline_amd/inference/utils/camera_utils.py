@@ -27,6 +27,7 @@ __all__ = [
     "fundamental_matrices",
     "fundamental_matrices_batched",
     "projection_matrices",
+    "pinhole_intrinsics",
     "rig_matrices",
 ]
 
@@ -171,6 +172,15 @@ def projection_matrices(Ks: np.ndarray, RTs: np.ndarray) -> np.ndarray:
     """P = K @ RT[:3] per camera (process_pose.py:91: float32 K promoted to
     float64 by the product with the float64 RT) -> float64 [S, C, 3, 4]."""
     return np.ascontiguousarray(np.asarray(Ks) @ np.asarray(RTs, dtype=np.float64)[..., :3, :])
+
+
+def pinhole_intrinsics(Ks: np.ndarray) -> np.ndarray:
+    """Per matrix of ``Ks`` [..., 3, 3]: True where it has the form the device
+    rig kernel inverts (include/mvmatch.h, mvm_rig_matrices): strict lower
+    triangle zero, no skew, ``K[2, 2] == 1``, non-zero focal lengths."""
+    K = np.asarray(Ks)
+    return ((K[..., 1, 0] == 0) & (K[..., 2, 0] == 0) & (K[..., 2, 1] == 0) & (K[..., 0, 1] == 0)
+            & (K[..., 2, 2] == 1) & (K[..., 0, 0] != 0) & (K[..., 1, 1] != 0))
 
 
 def rig_matrices(Ks: np.ndarray, RTs: np.ndarray):

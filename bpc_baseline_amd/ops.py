@@ -37,6 +37,7 @@ __all__ = [
     "pack_detections", "triangulate_dlt", "select_triangulate",
     "triplet_minima", "linear_sum_assignment_resid", "select_triangulate_resid",
     "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats", "compact_matches",
+    "rig_matrices",
 ]
 
 
@@ -522,6 +523,41 @@ def _(match, cost, X, count, seg_offs, pts, boxes, cam_offs, scene_base, dense_o
     return None
 
 
+@torch.library.custom_op("mvmatch::rig_matrices_out", mutates_args=("F", "proj", "status"))
+def rig_matrices_out(K: Tensor, RT: Tensor, pair_a: List[int], pair_b: List[int], F: Tensor,
+                     proj: Tensor, status: Tensor) -> None:
+    """F of every (capture, pair) and P = K @ RT[:3] of every (capture, camera)
+    on the device (mvm_rig_matrices).  ``proj`` empty: not produced."""
+    dev = K.device
+    if dev.type != "cuda":
+        raise ValueError("K must be a GPU tensor (the rig kernel has no CPU path)")
+    if K.dim() != 4 or tuple(K.shape[2:]) != (3, 3):
+        raise ValueError(f"K: expected [S, C, 3, 3], got {tuple(K.shape)}")
+    S, C = int(K.shape[0]), int(K.shape[1])
+    if tuple(RT.shape) != (S, C, 4, 4):
+        raise ValueError(f"RT: expected {(S, C, 4, 4)}, got {tuple(RT.shape)}")
+    n_pairs = len(pair_a)
+    if len(pair_b) != n_pairs:
+        raise ValueError("pair_a / pair_b differ in length")
+    for t, name, dt, numel in ((K, "K", torch.float32, 9 * S * C), (RT, "RT", torch.float64, 16 * S * C),
+                               (F, "F", torch.float64, 9 * S * n_pairs),
+                               (proj, "proj", torch.float64, 12 * S * C if proj.numel() else 0),
+                               (status, "status", torch.int32, S)):
+        _require(t, name, dt, dev)
+        if t.numel() != numel:
+            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+    pa = (ctypes.c_int32 * n_pairs)(*pair_a)
+    pb = (ctypes.c_int32 * n_pairs)(*pair_b)
+    st = _native.load().mvm_rig_matrices(_p(K), _p(RT), pa, pb, S, C, n_pairs, _p(F), _p(proj),
+                                         _p(status), _stream(K))
+    _native.check("mvm_rig_matrices", st)
+
+
+@rig_matrices_out.register_fake
+def _(K, RT, pair_a, pair_b, F, proj, status):
+    return None
+
+
 # ---------------------------------------------------------------- plans ----
 class PairwisePlan:
     """Offsets of every (scene, pair) residual matrix and argmin row block.
@@ -940,6 +976,64 @@ def select_triangulate_resid(tplan: TripletPlan, cam_offs: Tensor, lsap_offs: Te
                                                    row_ind, col_ind, pts, proj.contiguous(),
                                                    float(threshold), match, cost, X, count)
     return match, cost, X, count
+
+
+def _h2d_rig(Ks: np.ndarray, RTs: np.ndarray, device: torch.device) -> Tuple[Tensor, Tensor]:
+    """Host K (f32) and RT (f64) -> device tensors with ONE copy, as
+    ``_h2d_int64``: both in a pinned byte buffer (RT first: 8-byte aligned),
+    copied without blocking."""
+    rt = np.ascontiguousarray(RTs, dtype=np.float64)
+    k = np.ascontiguousarray(Ks, dtype=np.float32)
+    if rt.size == 0 or k.size == 0:      # nothing to stage (an empty batch)
+        return torch.from_numpy(k).to(device), torch.from_numpy(rt).to(device)
+    host =torch.from_numpy(np.concatenate([rt.reshape(-1).view(np.uint8), k.reshape(-1).view(np.uint8)]))
+    if device.type == "cuda":
+        dev = host.pin_memory().to(device, non_blocking=True)
+    else:
+        dev = host.to(device)
+    return (dev[rt.nbytes:].view(torch.float32).view(k.shape),
+            dev[:rt.nbytes].view(torch.float64).view(rt.shape))
+
+
+def rig_matrices(Ks, RTs, pairs=None, *, want_proj: bool = True,
+                 device: Optional[torch.device] = None):
+    """compute_fundamental_matrix for every (capture, pair) and P = K @ RT[:3]
+    for every (capture, camera), on the device (mvm_rig_matrices).
+
+    ``Ks`` float32 [S, C, 3, 3], ``RTs`` float64 [S, C, 4, 4]: numpy arrays
+    (uploaded in one pinned non-blocking copy, to ``device`` or the tensor
+    input's device or the current GPU) or device tensors.  ``pairs``
+    [P, 2]: default ``camera_pairs(C)``.
+    -> (F f64 [S*P, 9], proj f64 [S, C, 3, 4] or None, status i32 [S]), all on
+    the device.  status[s] = 1: some K of capture s is not of the pinhole form
+    (include/mvmatch.h) and its F / proj rows are NOT written."""
+    tensors = [x for x in (Ks, RTs) if isinstance(x, Tensor)]
+    if device is None:
+        device = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("rig_matrices needs a GPU device (the rig kernel has no CPU path)")
+    for x, name, dt in ((Ks, "K", np.float32), (RTs, "RT", np.float64)):
+        if not isinstance(x, Tensor) and np.asarray(x).dtype != dt:
+            raise ValueError(f"{name}: expected {np.dtype(dt)}, got {np.asarray(x).dtype}")
+    if not tensors:
+        K, RT = _h2d_rig(np.asarray(Ks), np.asarray(RTs), device)
+    else:       # one of them already on the device: the other goes up on its own
+        K, RT = (x if isinstance(x, Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(device)
+                 for x in (Ks, RTs))
+    if K.dim() != 4 or tuple(K.shape[2:]) != (3, 3):
+        raise ValueError(f"K: expected [S, C, 3, 3], got {tuple(K.shape)}")
+    S, C = int(K.shape[0]), int(K.shape[1])
+    if pairs is None:
+        pairs = [(a, b) for a in range(C) for b in range(a + 1, C)]    # camera_pairs(C)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n_pairs = int(pairs.shape[0])
+    F = torch.empty((S * n_pairs, 9), dtype=torch.float64, device=device)
+    proj = torch.empty((S, C, 3, 4) if want_proj else (0,), dtype=torch.float64, device=device)
+    status = torch.empty(S, dtype=torch.int32, device=device)
+    torch.ops.mvmatch.rig_matrices_out(K, RT, [int(a) for a in pairs[:, 0]],
+                                       [int(b) for b in pairs[:, 1]], F, proj, status)
+    return F, (proj if want_proj else None), status
 
 
 def compact_matches(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_offs: Tensor,

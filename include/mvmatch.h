@@ -40,6 +40,8 @@ extern "C" {
 #endif
 
 #define MVM_ABI_VERSION 8
+#define MVM_HAS_RIG_MATRICES 1 /* mvm_rig_matrices: an addition to ABI 8 (no existing
+                                  signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -517,6 +519,46 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
                         int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
                         int32_t *match_out_dev, float *cost_out_dev, double *X_out_dev,
                         int32_t *boxes_out_dev, double *cent_out_dev, mvm_stream_t stream);
+
+/*
+ * Fundamental and projection matrices on the device (an addition to ABI 8,
+ * announced by MVM_HAS_RIG_MATRICES): compute_fundamental_matrix
+ * (camera_utils.py:23-46) for every (capture, pair) and P = K @ RT[:3]
+ * (process_pose.py:91) for every (capture, camera), replacing the host's
+ * per-capture numpy products.  K_dev f32 [S, C, 3, 3], RT_dev f64 [S, C, 4, 4]
+ * (row-major [R|t] over (0, 0, 0, 1)); pair_a / pair_b are HOST arrays of
+ * n_pairs camera indices (a != b, validated here and passed by value), F
+ * mapping camera pair_a[p] points to camera pair_b[p] lines.  Outputs:
+ * F_dev f64 [S * n_pairs, 9] (the layout every matcher entry point reads),
+ * proj_dev f64 [S, C, 3, 4] (NULL: not produced; mvm_select_triangulate's and
+ * mvm_triangulate_dlt's input) and status_dev int32 [S].
+ * Arithmetic: the reference's, step by step and dtype by dtype, every dot
+ * product in index order k = 0, 1, 2.  The fp64 products of F are FMA chains
+ * (a0 * b0, then one fma per further term), as the OpenBLAS FMA kernels behind
+ * numpy's matmul evaluated them in the reference run; the float32 inverse and
+ * P round every product and sum on their own:
+ *   R_rel = R2 R1^T, t_rel = t2 - R_rel t1                      fp64 (:27-28)
+ *   skew(t_rel) cast to float32, promoted back                   (:31-35)
+ *   E = skew R_rel                                               fp64 (:37)
+ *   Kinv in float32 by back substitution dividing by the diagonal,
+ *     x[r] = (b[r] - sum_{q>r} K[r][q] x[q]) / K[r][r], promoted (:38-39)
+ *   F = (K2inv^T E) K1inv, left to right                         fp64 (:40)
+ *   F /= F[2][2] only when fabs(F[2][2]) > 1e-8                  (:43-44)
+ *   P = (double)K RT[:3, :]                           (process_pose.py:91)
+ * The back substitution is np.linalg.inv's result bit for bit only for a
+ * PINHOLE K: K[1][0] == K[2][0] == K[2][1] == 0, K[0][1] == 0, K[2][2] == 1,
+ * K[0][0] != 0 and K[1][1] != 0 (every BOP cam_K).  F and P then equal the
+ * host function's bit for bit where the host BLAS evaluates as above (the
+ * reference's recorded F does), and F to a few 1e-14 relative on a BLAS that
+ * sums otherwise.  status_dev[s] = 0: every K of capture
+ * s is pinhole and its rows are written; 1: some K is not, and NONE of that
+ * capture's F or proj rows is written -- the caller computes them
+ * (camera_utils.compute_fundamental_matrix).  One launch of S * (n_pairs + C)
+ * work items; n_scenes == 0 launches nothing.
+ */
+int mvm_rig_matrices(const float *K_dev, const double *RT_dev, const int32_t *pair_a,
+                     const int32_t *pair_b, int32_t n_scenes, int32_t n_cams, int32_t n_pairs,
+                     double *F_dev, double *proj_dev, int32_t *status_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

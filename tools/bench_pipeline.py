@@ -1,8 +1,10 @@
 """End-to-end batched capture matching (match_captures: pack -> cube -> LSAP ->
 select + DLT) on the GPU, with a parity spot-check and the CPU chain beside it.
 
-python tools/bench_pipeline.py [--captures 1000 --dets 24 --steps 5 --warmup 2]
+python tools/bench_pipeline.py [--captures 1000 --dets 24 --steps 5 --warmup 2] [--rig device]
 Prints one JSON line (captures/s, ms per batch, CPU captures/s on a sample).
+--rig device: F and P of every capture on the device (mvm_rig_matrices; the
+stage "F+P host" becomes "F+P device"); the static-rig line is the floor either way.
 """
 import argparse
 import json
@@ -52,6 +54,8 @@ def main():
                          "where the batch allows)")
     ap.add_argument("--rig-group", type=int, default=1,
                     help="consecutive captures sharing one camera rig (IPD: the images of a scene)")
+    ap.add_argument("--rig", choices=("host", "device"), default="host",
+                    help="where match_captures computes F and P (DESIGN §3.13)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     b = make_detector_batch(args.captures, args.dets, seed=5)
@@ -62,11 +66,11 @@ def main():
     boxes, conf, cls, offs = t(b.boxes), t(b.conf), t(b.cls), t(b.img_offs)
     res = None
     for _ in range(args.warmup):
-        res = match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, keep_cube=args.keep_cube)
+        res = match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, keep_cube=args.keep_cube, rig=args.rig)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        res = match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, keep_cube=args.keep_cube)
+        res = match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, keep_cube=args.keep_cube, rig=args.rig)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     # a static rig: F and P computed once and passed in
@@ -83,18 +87,18 @@ def main():
     # the same batches through the pipelined stream (host F/P of batch b+1
     # in worker processes while batch b runs on the device)
     batches = [(boxes, conf, cls, offs, b.Ks, b.RTs)] * args.steps
-    for _ in match_capture_stream(batches[:2]):
+    for _ in match_capture_stream(batches[:2], rig=args.rig):
         pass
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for r in match_capture_stream(batches):
+    for r in match_capture_stream(batches, rig=args.rig):
         res_stream = r
     torch.cuda.synchronize()
     dt_stream = (time.perf_counter() - t0) / args.steps
     # the same stream with F/P computed inline (no worker processes)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for r in match_capture_stream(batches, rig_workers=0):
+    for r in match_capture_stream(batches, rig_workers=0, rig=args.rig):
         pass
     torch.cuda.synchronize()
     dt_inline = (time.perf_counter() - t0) / args.steps
@@ -105,7 +109,7 @@ def main():
         assert np.array_equal(ms[o:o + k], mr[o:o + k]), s
     stages = {}
     for _ in range(args.steps):
-        match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, timings=stages, keep_cube=args.keep_cube)
+        match_captures(boxes, conf, cls, offs, b.Ks, b.RTs, timings=stages, keep_cube=args.keep_cube, rig=args.rig)
     stages = {k: round(v / args.steps * 1e3, 3) for k, v in stages.items()}
 
     # parity spot-check on a few captures, then the CPU chain on a sample
@@ -127,7 +131,7 @@ def main():
         "metric": "captures matched/sec (detect-pack + cube + LSAP + select + DLT)",
         "value": args.captures / dt, "unit": "captures/s", "ms_per_batch": dt * 1e3,
         "config": {"captures": args.captures, "dets_per_view": args.dets, "cams": 3, "keep_cube": args.keep_cube,
-                   "captures_per_rig": args.rig_group},
+                   "captures_per_rig": args.rig_group, "rig": args.rig},
         "matches": int(res.count.sum()), "parity_checked": len(check),
         "stage_ms_synchronised": stages,
         "stream": {"value": args.captures / dt_stream, "ms_per_batch": dt_stream * 1e3,

@@ -30,6 +30,9 @@
 #   bash tools/gpu.sh sharded [tool args]     match_captures_sharded: captures/s, each rank's
 #                                             chain / table / gather split, the match table
 #                                             against MatchBatch.host() (tools/bench_sharded_match.py)
+#   bash tools/gpu.sh rig [tool args]         F and P on the device: its suite, then
+#                                             tools/bench_pipeline.py --rig host / device in
+#                                             alternating processes at RIG_SIZES
 #   AB_LIBS="a.so b.so" bash tools/gpu.sh ab CMD...
 #                                             in-tree library builds (MVM_LIB_PATH) timed by
 #                                             CMD in alternating processes, AB_ROUNDS rounds
@@ -229,6 +232,23 @@ sharded)
   timeout -k 10 "$LIMIT" python -u tools/bench_sharded_match.py "$@" > "$O/sharded_match.json" \
     2> "$O/sharded_match.err" || fail "bench_sharded_match" "$O/sharded_match.err"
   tail -1 "$O/sharded_match.json" ;;
+rig)
+  # F and P on the device (mvm_rig_matrices): its suite, then the pipeline line under
+  # --rig host and --rig device in alternating processes, at each "captures:dets"
+  timeout -k 10 300 python -u -m pytest tests/test_rig_matrices_gpu.py -x -q -s --timeout 120 \
+    --timeout-method thread > "$O/pytest_rig.log" 2>&1 || fail "rig suite" "$O/pytest_rig.log"
+  tail -1 "$O/pytest_rig.log"
+  for spec in ${RIG_SIZES:-1000:24 1000:64}; do
+    for rnd in 1 2; do
+      for R in host device; do
+        timeout -k 10 "$LIMIT" python -u tools/bench_pipeline.py --captures "${spec%%:*}" --dets "${spec#*:}" \
+          --steps "${RIG_STEPS:-20}" --warmup 3 --cpu-sample 5 --rig $R "$@" \
+          >> "$O/rig_${spec#*:}_$R.json" 2>> "$O/rig_${spec#*:}_$R.err" || fail "rig $spec $R" "$O/rig_${spec#*:}_$R.err"
+        echo "== ${spec%%:*} x ${spec#*:} rig=$R round $rnd"
+        tail -1 "$O/rig_${spec#*:}_$R.json" | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['ms_per_batch'],3), 'ms/batch; static rig', round(d['static_rig']['ms_per_batch'],3), '; stages', d['stage_ms_synchronised'])"
+      done
+    done
+  done ;;
 ab)
   for rnd in $(seq 1 "${AB_ROUNDS:-3}"); do
     for lib in $AB_LIBS; do
