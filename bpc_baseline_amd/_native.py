@@ -172,6 +172,14 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp,                 # K, RT, pair_a (host), pair_b (host)
         _i32, _i32, _i32,                   # n_scenes, n_cams, n_pairs
         _vp, _vp, _vp, _vp]),               # F, proj (may be NULL), status, stream
+    "mvm_extend_costs": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp,  # pts, cam_offs, F_ext, match, match_offs, count, ext_offs
+        _i32, _i32, _i32, _vp, _vp]),       # n_scenes, n_cams, max_rows, E, stream
+    "mvm_extend_select_triangulate": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp,            # E, ext_offs, lsap_out_offs, row_ind, col_ind
+        _vp, _vp, _vp, _vp, _vp, _vp,       # match, match_offs, count, pts, cam_offs, proj
+        _i32, _i32, ctypes.c_double,        # n_scenes, n_cams, threshold
+        _vp, _vp, _vp, _vp]),               # views, ext_cost, X (in/out), stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

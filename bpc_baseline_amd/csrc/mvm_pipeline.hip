@@ -336,6 +336,99 @@ __global__ __launch_bounds__(kSelThreads) void select_triangulate_kernel(
     if (t == 0) count[s] = s_kept;
 }
 
+// ------------------------------------------- extension: select + DLT ----
+// The tail of the extension into extra cameras, after
+// mvm_extend_costs and the assignment of every (n, n_d) matrix: per capture,
+// views[w] = (i, j, k, -1, ...) and ext_cost[w] = +inf for its count matches;
+// each assigned pair (w, l) of extra camera d with (double)E_d[w][l] <
+// threshold (select_triangulate's compare) sets views[w][d] = l and
+// ext_cost[w][d - 3]; a match that kept an extra view is triangulated again
+// over its V views in ascending camera order, a match that kept none keeps
+// the X it came with.  One workgroup per capture; a row is assigned at most
+// once per camera, so the scatter has no conflicting writers.
+
+// DLT of one match over the NV cameras whose bits `mask` holds, ascending: the
+// P and centroids are gathered by constant slot (the camera of a slot comes
+// from the mask, so no register array is indexed dynamically).
+template <int NV>
+__device__ __forceinline__ void extend_dlt(const double *proj_s, const double *pts,
+                                           const int64_t *co, const int32_t *vw, uint32_t mask,
+                                           double X[3]) {
+    double P[12 * NV], xy[2 * NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int cam = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        const int64_t row = co[cam] + vw[cam];
+        xy[2 * v] = pts[2 * row];
+        xy[2 * v + 1] = pts[2 * row + 1];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) P[12 * v + k] = proj_s[12 * cam + k];
+    }
+    dlt_point<NV>(P, xy, X);
+}
+
+__global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
+    const float *E, const int64_t *ext_offs, const int64_t *lsap_offs, const int64_t *row_ind,
+    const int64_t *col_ind, const int32_t *match, const int64_t *match_offs, const int32_t *count,
+    const double *pts, const int64_t *cam_offs, const double *proj, double threshold,
+    int32_t n_cams, int32_t *views, float *ext_cost, double *X) {
+    const int64_t s = blockIdx.x;
+    const int t = threadIdx.x;
+    const int n_ext = n_cams - 3;
+    const int64_t mo = match_offs[s];
+    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
+    const int64_t *co = cam_offs + s * n_cams;
+    for (int64_t w = t; w < n; w += kSelThreads) {
+        int32_t *vw = views + (mo + w) * n_cams;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vw[c] = match[3 * (mo + w) + c];
+        for (int c = 3; c < n_cams; ++c) vw[c] = -1;
+        for (int e = 0; e < n_ext; ++e) ext_cost[(mo + w) * n_ext + e] = INFINITY;
+    }
+    __syncthreads();
+    for (int e = 0; e < n_ext; ++e) {
+        const int64_t sd = s * n_ext + e;
+        const int64_t nd = co[3 + e + 1] - co[3 + e];
+        if (nd <= 0) continue;
+        const int64_t eo = ext_offs[sd], lo = lsap_offs[sd];
+        const int64_t rows = min<int64_t>(n, (ext_offs[sd + 1] - eo) / nd);   // E_d's rows
+        const int64_t na = min<int64_t>(min<int64_t>(rows, nd), lsap_offs[sd + 1] - lo);
+        for (int64_t m = t; m < na; m += kSelThreads) {
+            const int64_t r = row_ind[lo + m], l = col_ind[lo + m];
+            // a failed assignment leaves its pairs unspecified: never an index
+            if (r < 0 || r >= rows || l < 0 || l >= nd) continue;
+            const float v = E[eo + r * nd + l];
+            if ((double)v < threshold) {
+                views[(mo + r) * n_cams + 3 + e] = (int32_t)l;
+                ext_cost[(mo + r) * n_ext + e] = v;
+            }
+        }
+    }
+    __syncthreads();
+    const double *proj_s = proj + s * n_cams * 12;
+    for (int64_t w = t; w < n; w += kSelThreads) {
+        const int32_t *vw = views + (mo + w) * n_cams;
+        uint32_t mask = 7u;
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ok &= vw[c] >= 0 && vw[c] < co[c + 1] - co[c];
+        for (int c = 3; c < n_cams; ++c) mask |= (vw[c] >= 0 ? 1u : 0u) << c;
+        if (!ok || mask == 7u) continue;      // the three-view X stands
+        double out[3];
+        switch (__builtin_popcount(mask)) {
+            case 4: extend_dlt<4>(proj_s, pts, co, vw, mask, out); break;
+            case 5: extend_dlt<5>(proj_s, pts, co, vw, mask, out); break;
+            case 6: extend_dlt<6>(proj_s, pts, co, vw, mask, out); break;
+            case 7: extend_dlt<7>(proj_s, pts, co, vw, mask, out); break;
+            default: extend_dlt<8>(proj_s, pts, co, vw, mask, out); break;
+        }
+        X[3 * (mo + w) + 0] = out[0];
+        X[3 * (mo + w) + 1] = out[1];
+        X[3 * (mo + w) + 2] = out[2];
+    }
+}
+
 // ------------------------------------------------- match table ----
 // The select kernels leave scene s's matches at lsap_offs[s] with slack rows
 // behind them, as per-view indices.  This copies them to dense rows
@@ -670,6 +763,37 @@ int mvm_select_triangulate(const float *cube_dev, const int64_t *cube_offs_dev,
         cube_dev, cube_offs_dev, cam_offs_dev, lsap_out_offs_dev, row_ind_dev, col_ind_dev, pts_dev,
         proj_dev, threshold, match_dev, cost_dev, X_dev, count_dev, nullptr, 0, 0, 0);
     return mvm_check_launch("select_triangulate_kernel");
+}
+
+int mvm_extend_select_triangulate(const float *E_dev, const int64_t *ext_offs_dev,
+                                  const int64_t *lsap_out_offs_dev, const int64_t *row_ind_dev,
+                                  const int64_t *col_ind_dev, const int32_t *match_dev,
+                                  const int64_t *match_offs_dev, const int32_t *count_dev,
+                                  const double *pts_dev, const int64_t *cam_offs_dev,
+                                  const double *proj_dev, int32_t n_scenes, int32_t n_cams,
+                                  double threshold, int32_t *views_dev, float *ext_cost_dev,
+                                  double *X_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    if (n_scenes == 0 || n_cams == 3) return MVM_OK;
+    // E / row_ind / col_ind / pts may be NULL when every extra view or every
+    // capture is empty (nothing then reads them)
+    const struct {
+        const void *p;
+        const char *name;
+    } args[] = {{ext_offs_dev, "ext_offs_dev"},     {lsap_out_offs_dev, "lsap_out_offs_dev"},
+                {match_dev, "match_dev"},           {match_offs_dev, "match_offs_dev"},
+                {count_dev, "count_dev"},           {cam_offs_dev, "cam_offs_dev"},
+                {proj_dev, "proj_dev"},             {views_dev, "views_dev"},
+                {ext_cost_dev, "ext_cost_dev"},     {X_dev, "X_dev"}};
+    for (const auto &a : args)
+        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    extend_select_triangulate_kernel<<<n_scenes, kSelThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        E_dev, ext_offs_dev, lsap_out_offs_dev, row_ind_dev, col_ind_dev, match_dev, match_offs_dev,
+        count_dev, pts_dev, cam_offs_dev, proj_dev, threshold, n_cams, views_dev, ext_cost_dev, X_dev);
+    return mvm_check_launch("extend_select_triangulate_kernel");
 }
 
 int mvm_select_triangulate_resid(const double *resid_dev, int32_t max_n, const int64_t *cam_offs_dev,

@@ -35,10 +35,31 @@ import numpy as np
 import torch
 
 from .. import ops
-from .utils.camera_utils import pinhole_intrinsics, projection_matrices, rig_matrices
+from .utils.camera_utils import (fundamental_matrices_batched, pinhole_intrinsics, projection_matrices,
+                                 rig_matrices)
 
-__all__ = ["MatchBatch", "MatchTable", "match_capture_stream", "match_captures", "projection_matrices",
-           "rig_matrices", "rig_worker_pool"]
+__all__ = ["MatchBatch", "MatchTable", "extension_pairs", "match_capture_stream", "match_captures",
+           "projection_matrices", "rig_matrices", "rig_worker_pool"]
+
+
+def extension_pairs(n_cams: int) -> np.ndarray:
+    """The camera pairs whose F ``match_captures(n_cams=C)`` uses, in its
+    order -> int32 [3 + 3 (C - 3), 2]: (0,1), (0,2), (1,2) of the three-camera
+    chain, then per extra camera d = 3 .. C-1 its pairs with the three anchor
+    cameras (0,d), (1,d), (2,d)."""
+    if not 3 <= int(n_cams) <= 8:
+        raise ValueError(f"n_cams: expected 3..8, got {n_cams}")
+    out = [(0, 1), (0, 2), (1, 2)] + [(c, d) for d in range(3, int(n_cams)) for c in range(3)]
+    return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+
+def _host_rig(Ks: np.ndarray, RTs: np.ndarray, n_cams: int):
+    """F and P of every capture on the host: ``rig_matrices`` for three
+    cameras, the same batched functions over ``extension_pairs`` above."""
+    if n_cams == 3:
+        return rig_matrices(Ks, RTs)
+    return (fundamental_matrices_batched(Ks, RTs, extension_pairs(n_cams)),
+            projection_matrices(Ks, RTs))
 
 
 @dataclass
@@ -52,25 +73,44 @@ class MatchBatch:
     offs: np.ndarray             # int64 [S + 1]
     pts: torch.Tensor            # float64 [n, 2]   packed centroids
     boxes: torch.Tensor          # int32 [n, 4]     packed int boxes
-    cam_offs: np.ndarray         # int64 [3S + 1]   CSR of pts / boxes
+    cam_offs: np.ndarray         # int64 [C S + 1]  CSR of pts / boxes (C = n_cams views per capture)
     cube: Optional[torch.Tensor] = None
     # what ``table`` hands the compaction kernel, kept on the device by
     # match_captures (a batch built without them uploads the host copies)
     offs_dev: Optional[torch.Tensor] = None       # int64 [S + 1]
     count_dev: Optional[torch.Tensor] = None      # int32 [S]
-    cam_offs_dev: Optional[torch.Tensor] = None   # int64 [3S + 1]
+    cam_offs_dev: Optional[torch.Tensor] = None   # int64 [C S + 1]
+    # a rig of n_cams > 3 cameras (match_captures(n_cams=C)):
+    # the match's detection in every view, -1 where an extra view has none
+    # (views[:, :3] == match), and the extension cost of the kept ones (+inf
+    # where none)
+    views: Optional[torch.Tensor] = None          # int32 [cap, C]
+    ext_cost: Optional[torch.Tensor] = None       # float32 [cap, C - 3]
+    n_cams: int = 3
 
     def host(self) -> dict:
         """One D2H copy of everything ``predictions`` reads."""
         if not hasattr(self, "_host"):
-            self._host = {k: getattr(self, k).cpu().numpy() for k in ("match", "cost", "X", "pts", "boxes")}
+            keys = ("match", "cost", "X", "pts", "boxes") + (("views",) if self.n_cams > 3 else ())
+            self._host = {k: getattr(self, k).cpu().numpy() for k in keys}
         return self._host
 
     def predictions(self, s: int) -> List[tuple]:
         """Scene s as the reference's PosePrediction fields, in _match's order:
-        list of (boxes int32 [3, 4], centroids f64 [3, 2], t f64 [3])."""
+        list of (boxes int32 [3, 4], centroids f64 [3, 2], t f64 [3]).  A
+        batch of n_cams > 3: per match its V views, (boxes [V, 4], centroids
+        [V, 2], t, cams int64 [V]) with cams ascending."""
         o, n = int(self.offs[s]), int(self.count[s])
         h = self.host()
+        C = self.n_cams
+        if C > 3:
+            out = []
+            for q in range(n):
+                v = h["views"][o + q].astype(np.int64)
+                cams = np.nonzero(v >= 0)[0]
+                rows = self.cam_offs[C * s + cams] + v[cams]
+                out.append((h["boxes"][rows], h["pts"][rows], h["X"][o + q], cams))
+            return out
         rows = self.cam_offs[3 * s:3 * s + 3][None, :] + h["match"][o:o + n].astype(np.int64)
         return [(h["boxes"][rows[q]], h["pts"][rows[q]], h["X"][o + q]) for q in range(n)]
 
@@ -79,6 +119,9 @@ class MatchBatch:
         ``count.sum()`` matches in consecutive rows, each with its boxes and
         centroids, scene ids starting at ``scene_base``.  No host sync: the
         row count is ``count``, already on the host."""
+        if self.n_cams > 3:
+            raise NotImplementedError("MatchTable rows hold three views; a batch of "
+                                      f"n_cams={self.n_cams} has no table yet")
         S = int(self.count.size)
         offs = np.zeros(S + 1, np.int64)
         np.cumsum(self.count, out=offs[1:])
@@ -143,7 +186,8 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    conf_thresh: float = 0.1, matching_threshold: float = 30,
                    keep_cube: bool = False, timings: Optional[dict] = None,
                    F: Optional[torch.Tensor] = None,
-                   proj: Optional[torch.Tensor] = None, rig: str = "host") -> MatchBatch:
+                   proj: Optional[torch.Tensor] = None, rig: str = "host",
+                   n_cams: int = 3) -> MatchBatch:
     """Detect-packing + matching + triangulation of S 3-camera captures.
 
     ``boxes`` f32 [n, 4] xyxy, ``conf``/``cls`` f32 [n]: the detector outputs
@@ -169,7 +213,22 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     computed on the host when ``Ks`` / ``RTs`` are host arrays, and raises
     ``ValueError`` when they are device tensors.  ``F`` / ``proj`` cannot be
     combined with ``rig="device"`` or ``"auto"``.
+
+    ``n_cams`` = C, 3 <= C <= 8: captures of C cameras (``img_offs`` int64
+    [C S + 1], ``Ks`` [S, C, 3, 3], ``RTs`` [S, C, 4, 4]; ``F`` f64
+    [S (3 + 3 (C - 3)), 9] in the order of ``extension_pairs(C)``, ``proj``
+    [S, C, 3, 4]).  Cameras 0, 1, 2 are matched as above, unchanged; each
+    extra camera d then assigns its detections to those matches by the cost
+    of a cube entry anchored at the match's three detections (scipy's
+    assignment, kept below ``matching_threshold``), and a match is
+    triangulated over all the views it kept.  The result has
+    ``views`` / ``ext_cost`` / ``n_cams`` set; matches, costs and order are
+    those of the three cameras alone.
     """
+    n_cams = int(n_cams)
+    if not 3 <= n_cams <= 8:
+        raise ValueError(f"n_cams: expected 3..8, got {n_cams}")
+    C = n_cams
     if rig not in ("host", "device", "auto"):
         raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
     if rig != "host" and (F is not None or proj is not None):
@@ -186,15 +245,16 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
             clock[0] = now
 
     n_img = int(img_offs.numel()) - 1
-    if n_img % 3:
-        raise ValueError("img_offs must describe 3 images per capture")
-    S = n_img // 3
+    if n_img % C:
+        raise ValueError(f"img_offs must describe {C} images per capture")
+    S = n_img // C
+    n_pairs = 3 + 3 * (C - 3)
     on_device = isinstance(Ks, torch.Tensor) or isinstance(RTs, torch.Tensor)
     if rig == "host" or not on_device:
-        Ks = np.asarray(Ks, dtype=np.float32).reshape(S, 3, 3, 3)
-        RTs = np.asarray(RTs, dtype=np.float64).reshape(S, 3, 4, 4)
+        Ks = np.asarray(Ks, dtype=np.float32).reshape(S, C, 3, 3)
+        RTs = np.asarray(RTs, dtype=np.float64).reshape(S, C, 4, 4)
     else:
-        Ks, RTs = Ks.reshape(S, 3, 3, 3), RTs.reshape(S, 3, 4, 4)
+        Ks, RTs = Ks.reshape(S, C, 3, 3), RTs.reshape(S, C, 4, 4)
     if rig == "auto":
         rig = "device" if on_device or bool(pinhole_intrinsics(Ks).all()) else "host"
 
@@ -205,13 +265,14 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     if rig == "device":
         # F and P of every capture by one launch behind the packing; its
         # per-capture status rides on the count copy below (no extra sync)
-        F, proj, rig_status = ops.rig_matrices(Ks, RTs, device=dev)
+        F, proj, rig_status = ops.rig_matrices(Ks, RTs, pairs=extension_pairs(C) if C > 3 else None,
+                                               device=dev)
         mark("F+P device")
     else:
         # host work while the packing runs: F and P for every capture (once per
         # distinct rig)
         if F is None or proj is None:
-            F_h, P_h = rig_matrices(Ks, RTs)
+            F_h, P_h = _host_rig(Ks, RTs, C)
             if F is None:
                 F = torch.from_numpy(F_h).to(dev)
             if proj is None:
@@ -232,9 +293,10 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                              "are then computed on the host) or use rig='host'")
         if rig_bad.size:
             # the kernel left those captures' rows unwritten: the host's values
-            F_h, P_h = rig_matrices(Ks[rig_bad], RTs[rig_bad])
+            F_h, P_h = _host_rig(Ks[rig_bad], RTs[rig_bad], C)
             idx, = ops._h2d_int64([rig_bad], dev)
-            F.view(S, 27).index_copy_(0, idx, torch.from_numpy(F_h.reshape(-1, 27)).to(dev))
+            F.view(S, 9 * n_pairs).index_copy_(0, idx,
+                                               torch.from_numpy(F_h.reshape(-1, 9 * n_pairs)).to(dev))
             proj.index_copy_(0, idx, torch.from_numpy(P_h).to(dev))
     counts_host = ch[:-1]
     if ch[-1] != 0:
@@ -243,6 +305,21 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     np.cumsum(counts_host, out=cam_offs_host[1:])
     mark("counts D2H")
 
+    full = None
+    if C > 3:
+        # cameras 0, 1, 2 of every capture as a three-camera batch of its own
+        # (centroids, F and P gathered on the device); the existing chain runs
+        # on it untouched
+        full = (pts, cam_offs, cam_offs_host, counts_host.reshape(S, C), F_dev, proj_dev)
+        rows = np.nonzero(np.repeat(np.arange(S * C) % C < 3, counts_host))[0].astype(np.int64)
+        counts_host = np.ascontiguousarray(counts_host.reshape(S, C)[:, :3]).reshape(-1)
+        cam_offs_host = np.zeros(3 * S + 1, np.int64)
+        np.cumsum(counts_host, out=cam_offs_host[1:])
+        sel, cam_offs = ops._h2d_int64([rows, cam_offs_host], dev)
+        pts = pts.index_select(0, sel) if rows.size else pts[:0]
+        F_dev = F_dev.view(S, n_pairs, 9)[:, :3].reshape(-1)
+        proj_dev = proj_dev.view(S, C, 3, 4)[:, :3].contiguous()
+        mark("three-view gather")
     c3 = counts_host.reshape(S, 3)
     free = ops.cube_free_scenes(c3) if not keep_cube else np.zeros(S, bool)
     if free.all() or not free.any():
@@ -262,10 +339,56 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
         raise ValueError(f"assignment failed for captures {np.nonzero(bad)[0][:8].tolist()} "
                          "(cost matrix contains invalid numeric entries or is infeasible)")
     mark("results D2H")
+    if full is not None:
+        views, ext_cost = _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C,
+                                  float(matching_threshold), mark)
+        return MatchBatch(match=match, cost=cost, X=X, count=count_h, offs=out_offs_host, pts=full[0],
+                          boxes=boxes_int, cam_offs=full[2], cube=cube if keep_cube else None,
+                          offs_dev=out_offs, count_dev=count, cam_offs_dev=full[1], views=views,
+                          ext_cost=ext_cost, n_cams=C)
     return MatchBatch(match=match, cost=cost, X=X, count=count_h,
                       offs=out_offs_host, pts=pts, boxes=boxes_int, cam_offs=cam_offs_host,
                       cube=cube if keep_cube else None, offs_dev=out_offs, count_dev=count,
                       cam_offs_dev=cam_offs)
+
+
+def _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C, threshold, mark):
+    """The extension of the three-view matches into cameras 3 .. C-1 (DESIGN
+    §3.14): cost matrices -> assignment -> threshold + V-view DLT, behind the
+    results copy (``count_h``: the match counts on the host).  ``X`` is
+    updated in place.  -> (views int32 [cap, C], ext_cost f32 [cap, C - 3]).
+    One device -> host copy: the assignment statuses."""
+    pts, cam_offs, _, counts, F_dev, proj = full
+    dev = pts.device
+    n_ext = C - 3
+    cap = int(match.shape[0])
+    views = torch.empty((cap, C), dtype=torch.int32, device=dev)
+    ext_cost = torch.empty((cap, n_ext), dtype=torch.float32, device=dev)
+    rows = np.repeat(np.asarray(count_h, np.int64), n_ext)
+    cols = counts[:, 3:].reshape(-1).astype(np.int64)
+    # every matrix starts on a 16-byte boundary (aligned rows then store 16 bytes a lane)
+    ext_offs_host = np.zeros(S * n_ext + 1, np.int64)
+    np.cumsum((rows * cols + 3) // 4 * 4, out=ext_offs_host[1:])
+    max_rows = int(rows.max()) if rows.size else 0
+    if cap == 0 or max_rows == 0:
+        return views, ext_cost
+    ext_offs, = ops._h2d_int64([ext_offs_host], dev)
+    F_ext = F_dev.view(S, 3 + 3 * n_ext, 9)[:, 3:].contiguous()
+    E = ops.extend_costs(pts, cam_offs, F_ext, match, out_offs, count, ext_offs, C, max_rows,
+                         size=int(ext_offs_host[-1]))
+    mark("extend costs")
+    lplan = ops.LsapPlan(rows, cols, device=dev)
+    row_ind, col_ind, lstat = ops.linear_sum_assignment_batched(E, ext_offs[:-1].contiguous(), lplan)
+    mark("extend lsap")
+    ops.extend_select_triangulate(E, ext_offs, lplan.out_offs, row_ind, col_ind, match, out_offs, count,
+                                  pts, cam_offs, proj, threshold, X, C, out=(views, ext_cost))
+    mark("extend select")
+    bad = lstat.cpu().numpy().reshape(S, n_ext).any(axis=1)
+    if np.any(bad):
+        raise ValueError(f"assignment failed for captures {np.nonzero(bad)[0][:8].tolist()} "
+                         "(cost matrix contains invalid numeric entries or is infeasible)")
+    mark("extend D2H")
+    return views, ext_cost
 
 
 def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, cube_free, keep_cube,
@@ -358,12 +481,12 @@ def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
     return match[:cap], cost[:cap], X[:cap], status, count, out_offs, None, out_offs_dev
 
 
-def _rig_inputs(batch: Sequence):
-    """(Ks f32 [S,3,3,3], RTs f64 [S,3,4,4]) of one ``match_capture_stream`` batch."""
+def _rig_inputs(batch: Sequence, n_cams: int = 3):
+    """(Ks f32 [S,C,3,3], RTs f64 [S,C,4,4]) of one ``match_capture_stream`` batch."""
     boxes, conf, cls, img_offs, Ks, RTs = batch
-    S = (int(img_offs.numel()) - 1) // 3
-    return (np.asarray(Ks, dtype=np.float32).reshape(S, 3, 3, 3),
-            np.asarray(RTs, dtype=np.float64).reshape(S, 3, 4, 4))
+    S = (int(img_offs.numel()) - 1) // n_cams
+    return (np.asarray(Ks, dtype=np.float32).reshape(S, n_cams, 3, 3),
+            np.asarray(RTs, dtype=np.float64).reshape(S, n_cams, 4, 4))
 
 
 _TLS = threading.local()
@@ -417,12 +540,15 @@ def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3, r
     ``rig="device"`` / ``"auto"`` (``match_captures``' keyword): every batch
     is ``match_captures(..., rig=rig)``; there is no host F / P to overlap, so
     no worker pool is started or used (``rig_workers`` is ignored).
+
+    ``n_cams`` (in ``kwargs``) is passed through; the worker processes compute
+    three-camera rigs, so a stream of n_cams > 3 computes F / P inline.
     """
     if "F" in kwargs or "proj" in kwargs:
         raise TypeError("match_capture_stream computes F and proj itself")
     if rig not in ("host", "device", "auto"):
         raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
-    if rig != "host":
+    if rig != "host" or int(kwargs.get("n_cams", 3)) != 3:
         for cur in batches:
             yield match_captures(*cur, rig=rig, **kwargs)
         return

@@ -37,7 +37,7 @@ __all__ = [
     "pack_detections", "triangulate_dlt", "select_triangulate",
     "triplet_minima", "linear_sum_assignment_resid", "select_triangulate_resid",
     "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats", "compact_matches",
-    "rig_matrices",
+    "rig_matrices", "extend_costs", "extend_select_triangulate",
 ]
 
 
@@ -558,6 +558,93 @@ def _(K, RT, pair_a, pair_b, F, proj, status):
     return None
 
 
+@torch.library.custom_op("mvmatch::extend_costs_out", mutates_args=("E",))
+def extend_costs_out(pts: Tensor, cam_offs: Tensor, F_ext: Tensor, match: Tensor, match_offs: Tensor,
+                     count: Tensor, ext_offs: Tensor, n_cams: int, max_rows: int, E: Tensor) -> None:
+    """The extension cost matrices E_d of every (capture, extra camera)
+    (mvm_extend_costs)."""
+    dev = pts.device
+    if dev.type != "cuda":
+        raise ValueError("pts must be a GPU tensor (the matcher has no CPU path)")
+    n_scenes = count.numel()
+    n_ext = n_cams - 3
+    if n_ext < 0 or n_cams > _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if match.dim() != 2 or match.shape[1] != 3:
+        raise ValueError("match must be [cap, 3]")
+    for t, name, dt, numel in ((pts, "pts", torch.float64, 0),
+                               (cam_offs, "cam_offs", torch.int64, n_cams * n_scenes + 1),
+                               (F_ext, "F_ext", torch.float64, 27 * n_ext * n_scenes),
+                               (match, "match", torch.int32, 0),
+                               (match_offs, "match_offs", torch.int64, n_scenes + 1),
+                               (count, "count", torch.int32, n_scenes),
+                               (ext_offs, "ext_offs", torch.int64, n_ext * n_scenes + 1),
+                               (E, "E", torch.float32, 0)):
+        _require(t, name, dt, dev)
+        if numel and t.numel() != numel:
+            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+    if n_scenes == 0 or n_ext == 0 or max_rows == 0 or E.numel() == 0:
+        return                       # no matrix has an entry: nothing to launch
+    st = _native.load().mvm_extend_costs(_p(pts), _p(cam_offs), _p(F_ext), _p(match), _p(match_offs),
+                                         _p(count), _p(ext_offs), n_scenes, n_cams, int(max_rows),
+                                         _p(E), _stream(pts))
+    _native.check("mvm_extend_costs", st)
+
+
+@extend_costs_out.register_fake
+def _(pts, cam_offs, F_ext, match, match_offs, count, ext_offs, n_cams, max_rows, E):
+    return None
+
+
+@torch.library.custom_op("mvmatch::extend_select_triangulate_out",
+                         mutates_args=("views", "ext_cost", "X"))
+def extend_select_triangulate_out(E: Tensor, ext_offs: Tensor, lsap_offs: Tensor, row_ind: Tensor,
+                                  col_ind: Tensor, match: Tensor, match_offs: Tensor, count: Tensor,
+                                  pts: Tensor, cam_offs: Tensor, proj: Tensor, threshold: float,
+                                  views: Tensor, ext_cost: Tensor, X: Tensor) -> None:
+    """Threshold + scatter of the extension's assignments and the V-view DLT
+    (mvm_extend_select_triangulate).  ``X`` is in/out."""
+    dev = match.device
+    if dev.type != "cuda":
+        raise ValueError("match must be a GPU tensor (the matcher has no CPU path)")
+    n_scenes = count.numel()
+    if views.dim() != 2 or not 3 <= views.shape[1] <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"views must be [cap, C], 3 <= C <= {_native.MVM_MAX_CAMS}")
+    cap, n_cams = int(views.shape[0]), int(views.shape[1])
+    n_ext = n_cams - 3
+    if match.dim() != 2 or tuple(match.shape) != (cap, 3):
+        raise ValueError(f"match must be [{cap}, 3] (the rows of views)")
+    for t, name, dt, numel in ((E, "E", torch.float32, -1), (ext_offs, "ext_offs", torch.int64, n_ext * n_scenes + 1),
+                               (lsap_offs, "lsap_offs", torch.int64, n_ext * n_scenes + 1),
+                               (row_ind, "row_ind", torch.int64, -1), (col_ind, "col_ind", torch.int64, -1),
+                               (match, "match", torch.int32, 3 * cap),
+                               (match_offs, "match_offs", torch.int64, n_scenes + 1),
+                               (count, "count", torch.int32, n_scenes), (pts, "pts", torch.float64, -1),
+                               (cam_offs, "cam_offs", torch.int64, n_cams * n_scenes + 1),
+                               (proj, "proj", torch.float64, 12 * n_cams * n_scenes),
+                               (views, "views", torch.int32, n_cams * cap),
+                               (ext_cost, "ext_cost", torch.float32, n_ext * cap),
+                               (X, "X", torch.float64, 3 * cap)):
+        _require(t, name, dt, dev)
+        if numel >= 0 and t.numel() != numel:
+            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+    if col_ind.numel() != row_ind.numel():
+        raise ValueError("row_ind / col_ind differ in length")
+    if n_scenes == 0 or n_ext == 0 or cap == 0:
+        return                       # no row to fill: nothing to launch
+    st = _native.load().mvm_extend_select_triangulate(
+        _p(E), _p(ext_offs), _p(lsap_offs), _p(row_ind), _p(col_ind), _p(match), _p(match_offs),
+        _p(count), _p(pts), _p(cam_offs), _p(proj), n_scenes, n_cams, float(threshold), _p(views),
+        _p(ext_cost), _p(X), _stream(match))
+    _native.check("mvm_extend_select_triangulate", st)
+
+
+@extend_select_triangulate_out.register_fake
+def _(E, ext_offs, lsap_offs, row_ind, col_ind, match, match_offs, count, pts, cam_offs, proj, threshold,
+      views, ext_cost, X):
+    return None
+
+
 # ---------------------------------------------------------------- plans ----
 class PairwisePlan:
     """Offsets of every (scene, pair) residual matrix and argmin row block.
@@ -1064,3 +1151,53 @@ def compact_matches(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_o
                                               X_out, boxes_out, cent_out)
     return (dense_offs, scene[:cap], match_out[:cap], cost_out[:cap], X_out[:cap], boxes_out[:cap],
             cent_out[:cap])
+
+
+def extend_costs(pts: Tensor, cam_offs: Tensor, F_ext: Tensor, match: Tensor, match_offs: Tensor,
+                 count: Tensor, ext_offs: Tensor, n_cams: int, max_rows: int, *,
+                 size: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The cost of extending each three-view match into each detection of the
+    extra cameras 3 .. n_cams-1 (mvm_extend_costs): for capture
+    s and camera d the float32 matrix ``E_d [count[s], n_d]`` at
+    ``ext_offs[s * (n_cams - 3) + d - 3]`` of the result, a cube entry whose
+    anchors are the match's own detections.  ``pts`` / ``cam_offs`` the
+    n_cams-camera CSR, ``F_ext`` f64 [S, n_cams-3, 3, 9] (F_0d, F_1d, F_2d per
+    extra camera), ``match`` int32 [cap, 3] / ``match_offs`` int64 [S+1] /
+    ``count`` int32 [S] as select_triangulate left them, ``max_rows`` a host
+    bound on ``count``.  ``size`` = ``ext_offs[-1]`` when the caller knows it
+    on the host (otherwise it is read back: one sync); ``out``: the float32
+    buffer to write.  Entries outside the matrices are not written."""
+    if out is None:
+        if size is None:
+            size = int(ext_offs[-1].item())
+        out = torch.empty(max(int(size), 1), dtype=torch.float32, device=pts.device)
+    torch.ops.mvmatch.extend_costs_out(pts, cam_offs, F_ext, match, match_offs, count, ext_offs,
+                                       int(n_cams), int(max_rows), out)
+    return out
+
+
+def extend_select_triangulate(E: Tensor, ext_offs: Tensor, lsap_offs: Tensor, row_ind: Tensor,
+                              col_ind: Tensor, match: Tensor, match_offs: Tensor, count: Tensor,
+                              pts: Tensor, cam_offs: Tensor, proj: Tensor, threshold: float,
+                              X: Tensor, n_cams: int, *,
+                              out: Optional[Tuple[Tensor, Tensor]] = None):
+    """The tail of the extension (mvm_extend_select_triangulate): the
+    assignment (``row_ind`` / ``col_ind`` under ``lsap_offs``) of every
+    ``extend_costs`` matrix, kept where ``E < threshold``.
+    -> (views int32 [cap, n_cams] = (i, j, k, kept index or -1 ...),
+    ext_cost f32 [cap, n_cams-3] = the kept E or +inf, X): ``X`` f64 [cap, 3]
+    is updated in place -- matches that kept an extra view are triangulated
+    over all their views, the others keep their value.  ``out`` = (views,
+    ext_cost) to write into; rows outside the captures' matches keep their
+    values."""
+    dev = match.device
+    cap = int(match.shape[0])
+    if out is None:
+        views = torch.empty((cap, n_cams), dtype=torch.int32, device=dev)
+        ext_cost = torch.empty((cap, n_cams - 3), dtype=torch.float32, device=dev)
+    else:
+        views, ext_cost = out
+    torch.ops.mvmatch.extend_select_triangulate_out(E, ext_offs, lsap_offs, row_ind, col_ind, match,
+                                                    match_offs, count, pts, cam_offs, proj.contiguous(),
+                                                    float(threshold), views, ext_cost, X)
+    return views, ext_cost, X

@@ -42,6 +42,8 @@ extern "C" {
 #define MVM_ABI_VERSION 8
 #define MVM_HAS_RIG_MATRICES 1 /* mvm_rig_matrices: an addition to ABI 8 (no existing
                                   signature or struct changed) */
+#define MVM_HAS_EXTEND 1 /* mvm_extend_costs, mvm_extend_select_triangulate: additions to
+                            ABI 8 (no existing signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -559,6 +561,67 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
 int mvm_rig_matrices(const float *K_dev, const double *RT_dev, const int32_t *pair_a,
                      const int32_t *pair_b, int32_t n_scenes, int32_t n_cams, int32_t n_pairs,
                      double *F_dev, double *proj_dev, int32_t *status_dev, mvm_stream_t stream);
+
+/*
+ * Extension of three-view matches into the extra cameras of a C-camera rig,
+ * 4 <= C <= MVM_MAX_CAMS (additions to ABI 8, announced by MVM_HAS_EXTEND).
+ * Cameras 0, 1, 2 of every capture go through the three-camera chain above,
+ * which leaves capture s's count_dev[s] matches (i, j, k) at rows
+ * match_offs_dev[s] + w of match_dev (the lsap_out_offs_dev given to
+ * mvm_select_triangulate).  For each extra camera d = 3 .. C-1 with n_d
+ * detections q_l, mvm_extend_costs writes the float32 matrix
+ *   E_d[w][l] = float32(((e_0d(p0[i_w], q_l) + e_1d(p1[j_w], q_l)) + e_2d(p2[k_w], q_l)) / 3)
+ * with e_cd(p, q) = epipolar_error(p, q, F_cd) in fp64, the 9999 sentinel
+ * included (epipolar_matching.py:5-28): the arithmetic of a cube entry
+ * (:78-81, :96) with the match's own detections as the three anchors, NaN /
+ * inf propagated as the cube does.  An (i, j, k) outside its view counts as a
+ * NaN centroid.
+ *   pts_dev / cam_offs_dev   the C-camera CSR (cam_offs_dev int64 [C*S + 1]);
+ *   F_ext_dev   f64 [S, C-3, 3, 9]: per capture F_0d, F_1d, F_2d for d = 3, 4, ..
+ *               (pairs (0,3), (1,3), (2,3), (0,4), ...), F_cd mapping camera c
+ *               points to camera d lines;
+ *   ext_offs_dev int64 [S*(C-3) + 1]: E_d of capture s starts at float
+ *               ext_offs[s*(C-3) + d-3] of E_dev, row-major [count[s]][n_d],
+ *               contiguous -- what mvm_lsap_solve* reads through cost_offs /
+ *               dims.  The region must hold count[s] * n_d floats; rows it has
+ *               no room for are not written.  Rows of a matrix with n_d % 4 ==
+ *               0 that starts on a 16-byte boundary are stored 16 bytes per
+ *               lane, others element by element;
+ *   max_rows    a host bound on count[s] (sizes the grid; rows at and beyond
+ *               count[s] are never written, nor is anything outside the
+ *               matrices).
+ * One launch, a workgroup per 64 rows of one (capture, d).  n_scenes == 0,
+ * C == 3 or max_rows == 0 launch nothing.
+ */
+int mvm_extend_costs(const double *pts_dev, const int64_t *cam_offs_dev, const double *F_ext_dev,
+                     const int32_t *match_dev, const int64_t *match_offs_dev,
+                     const int32_t *count_dev, const int64_t *ext_offs_dev, int32_t n_scenes,
+                     int32_t n_cams, int32_t max_rows, float *E_dev, mvm_stream_t stream);
+/*
+ * ... its tail, after the assignment of every E_d (mvm_lsap_solve* over the
+ * S*(C-3) problems (count[s], n_d): row_ind_dev / col_ind_dev under
+ * lsap_out_offs_dev int64 [S*(C-3) + 1]).  For match w of capture s, at row
+ * r = match_offs[s] + w: views_dev int32 [.., C] = (i, j, k, -1, ...) and
+ * ext_cost_dev f32 [.., C-3] = +inf; then each assigned pair (w, l) of camera
+ * d with (double)E_d[w][l] < threshold (mvm_select_triangulate's compare:
+ * NaN on either side keeps nothing) sets views[r][d] = l and
+ * ext_cost[r][d-3] = E_d[w][l].  X_dev f64 [.., 3] is in/out: a match that
+ * kept an extra view gets the DLT (mvm_triangulate_dlt's) over cameras
+ * {0, 1, 2} and its kept ones in ascending order with proj_dev [S, C, 3, 4];
+ * a match that kept none keeps the value X_dev held, bit for bit.  Rows
+ * outside [match_offs[s], match_offs[s] + count[s]) of views / ext_cost / X
+ * are not written.  Assigned pairs that are not indices of E_d (a failed
+ * assignment's) are ignored.  One workgroup per capture; n_scenes == 0 or
+ * C == 3 launch nothing.
+ */
+int mvm_extend_select_triangulate(const float *E_dev, const int64_t *ext_offs_dev,
+                                  const int64_t *lsap_out_offs_dev, const int64_t *row_ind_dev,
+                                  const int64_t *col_ind_dev, const int32_t *match_dev,
+                                  const int64_t *match_offs_dev, const int32_t *count_dev,
+                                  const double *pts_dev, const int64_t *cam_offs_dev,
+                                  const double *proj_dev, int32_t n_scenes, int32_t n_cams,
+                                  double threshold, int32_t *views_dev, float *ext_cost_dev,
+                                  double *X_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

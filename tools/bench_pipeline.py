@@ -5,6 +5,9 @@ python tools/bench_pipeline.py [--captures 1000 --dets 24 --steps 5 --warmup 2] 
 Prints one JSON line (captures/s, ms per batch, CPU captures/s on a sample).
 --rig device: F and P of every capture on the device (mvm_rig_matrices; the
 stage "F+P host" becomes "F+P device"); the static-rig line is the floor either way.
+--cams C (4..8): captures of C cameras from make_capture, matched with
+match_captures(n_cams=C); --first-three matches only cameras 0-2
+of the same captures, the three-camera line the extension is measured against.
 """
 import argparse
 import json
@@ -42,8 +45,77 @@ def cpu_chain(b, s):
     return m, X
 
 
+def wide_batch(captures, dets, C, seed=5):
+    """Detector outputs of `captures` C-camera captures (make_capture: half of
+    every view true objects, half clutter), capture s from default_rng(seed + s)
+    -> (boxes f32 [n, 4], conf, cls, img_offs i64 [C S + 1], Ks, RTs)."""
+    from bpc_baseline_amd.synth import make_capture
+    boxes, counts = [], []
+    Ks, RTs = np.empty((captures, C, 3, 3), np.float32), np.empty((captures, C, 4, 4))
+    for s in range(captures):
+        k, rt, det = make_capture(np.random.default_rng(seed + s), C, dets)
+        Ks[s], RTs[s] = np.stack(k), np.stack(rt)
+        for c in range(C):
+            boxes.append(np.array([d["bbox"] for d in det[c]], np.float32).reshape(-1, 4))
+            counts.append(len(det[c]))
+    offs = np.zeros(captures * C + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    boxes = np.concatenate(boxes)
+    return boxes, np.full(len(boxes), 0.9, np.float32), np.zeros(len(boxes), np.float32), offs, Ks, RTs
+
+
+def main_wide(args):
+    """--cams C > 3: ms per batch and synchronised stage times of
+    match_captures(n_cams=C), or (--first-three) of the three-camera chain on
+    cameras 0-2 of the same captures."""
+    dev = torch.device("cuda", 0)
+    C = args.cams
+    boxes, conf, cls, offs, Ks, RTs = wide_batch(args.captures, args.dets, C)
+    kw = dict(keep_cube=args.keep_cube, rig=args.rig)
+    if args.first_three:
+        rows = np.concatenate([np.arange(offs[C * s], offs[C * s + 3]) for s in range(args.captures)])
+        n3 = np.diff(offs).reshape(-1, C)[:, :3].reshape(-1)
+        offs = np.concatenate([[0], np.cumsum(n3)]).astype(np.int64)
+        boxes, conf, cls = boxes[rows], conf[rows], cls[rows]
+        Ks, RTs = np.ascontiguousarray(Ks[:, :3]), np.ascontiguousarray(RTs[:, :3])
+    else:
+        kw["n_cams"] = C
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    inp = (t(boxes), t(conf), t(cls), t(offs), Ks, RTs)
+    for _ in range(args.warmup):
+        res = match_captures(*inp, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        res = match_captures(*inp, **kw)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.steps
+    stages = {}
+    for _ in range(args.steps):
+        match_captures(*inp, timings=stages, **kw)
+    stages = {k: round(v / args.steps * 1e3, 3) for k, v in stages.items()}
+    out = {"metric": "captures matched/sec (detect-pack + cube + LSAP + select + DLT"
+                     + ("" if args.first_three else " + extension") + ")",
+           "value": args.captures / dt, "unit": "captures/s", "ms_per_batch": dt * 1e3,
+           "config": {"captures": args.captures, "dets_per_view": args.dets, "cams": C,
+                      "matched_cams": 3 if args.first_three else C, "keep_cube": args.keep_cube,
+                      "rig": args.rig},
+           "matches": int(res.count.sum()), "stage_ms_synchronised": stages}
+    if not args.first_three:
+        v = res.views.cpu().numpy()
+        keep = np.concatenate([np.arange(o, o + n) for o, n in zip(res.offs[:-1], res.count)]
+                              + [np.zeros(0, np.int64)]).astype(np.int64)
+        out["matches_with_an_extra_view"] = int((v[keep, 3:] >= 0).any(axis=1).sum())
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cams", type=int, default=3, choices=range(3, 9),
+                    help="cameras per capture; above 3: make_capture captures through "
+                         "match_captures(n_cams=C) (DESIGN §3.14)")
+    ap.add_argument("--first-three", action="store_true",
+                    help="with --cams C > 3: match cameras 0-2 of the same captures only")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -57,6 +129,8 @@ def main():
     ap.add_argument("--rig", choices=("host", "device"), default="host",
                     help="where match_captures computes F and P (DESIGN §3.13)")
     args = ap.parse_args()
+    if args.cams > 3:
+        return main_wide(args)
     dev = torch.device("cuda", 0)
     b = make_detector_batch(args.captures, args.dets, seed=5)
     if args.rig_group > 1:   # rig of the group's first capture (match_captures dedupes F/P)
