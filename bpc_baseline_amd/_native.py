@@ -180,6 +180,13 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, _vp, _vp,       # match, match_offs, count, pts, cam_offs, proj
         _i32, _i32, ctypes.c_double,        # n_scenes, n_cams, threshold
         _vp, _vp, _vp, _vp]),               # views, ext_cost, X (in/out), stream
+    "mvm_compact_matches_views": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp, _vp,       # views, cost, ext_cost (may be NULL), X, count, seg_offs
+        _vp, _vp, _vp, _vp,                 # pts, boxes, cam_offs, proj
+        _i32, _i32, _i32,                   # n_scenes, n_cams, scene_base
+        _vp, _vp, _vp, _vp, _vp,            # dense_offs, scene, views, n_views, cost (out)
+        _vp, _vp, _vp, _vp, _vp,            # ext_cost (may be NULL), X, boxes, cent, reproj (out)
+        _vp]),                              # stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

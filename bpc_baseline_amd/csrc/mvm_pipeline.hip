@@ -482,6 +482,102 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
     }
 }
 
+// The table of a C-camera batch (mvm_compact_matches_views): the same copy
+// over the C view slots of mvm_extend_select_triangulate's rows, -1 slots
+// filled with (-1, -1, -1, -1) / NaN, plus the reprojection residual of X in
+// every kept view.  The capture's P (12 C doubles) and cam_offs are the same
+// for every lane of the wave: loaded once, ahead of the match loop and of
+// every store.  The camera slot is a compile-time index (MVM_MAX_CAMS slots,
+// `c < n_cams` predicated), so P and co stay in registers.  Every product and
+// sum of the residual is rounded on its own (this file's fp contract(off)).
+template <bool VEC>
+__global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
+    const int32_t *__restrict__ views, const float *__restrict__ cost,
+    const float *__restrict__ ext_cost, const double *__restrict__ X,
+    const int32_t *__restrict__ count, const int64_t *__restrict__ seg_offs,
+    const int64_t *__restrict__ dense_offs, const double *__restrict__ pts,
+    const int32_t *__restrict__ boxes, const int64_t *__restrict__ cam_offs,
+    const double *__restrict__ proj, int32_t n_scenes, int32_t n_cams, int32_t scene_base,
+    int32_t *__restrict__ scene_out, int32_t *__restrict__ views_out, int32_t *__restrict__ nviews_out,
+    float *__restrict__ cost_out, float *__restrict__ ext_cost_out, double *__restrict__ X_out,
+    int32_t *__restrict__ boxes_out, double *__restrict__ cent_out, double *__restrict__ reproj_out) {
+    const int lane = threadIdx.x % 64;
+    // the wave's capture as a scalar, so its P and offsets are scalar loads
+    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
+                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    if (s >= n_scenes) return;
+    const int64_t src = seg_offs[s], dst = dense_offs[s];
+    const int32_t n = count[s];
+    const int n_ext = n_cams - 3;
+    int64_t co[MVM_MAX_CAMS];
+    double P[12 * MVM_MAX_CAMS];
+#pragma unroll
+    for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+        if (c < n_cams) {
+            co[c] = cam_offs[s * n_cams + c];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) P[12 * c + k] = proj[(s * n_cams + c) * 12 + k];
+        }
+    }
+    const double qnan = __builtin_nan("");
+    for (int32_t w = lane; w < n; w += 64) {
+        const int64_t a = src + w, r = dst + w;
+        const double X0 = X[3 * a], X1 = X[3 * a + 1], X2 = X[3 * a + 2];
+        scene_out[r] = scene_base + (int32_t)s;
+        cost_out[r] = cost[a];
+        X_out[3 * r] = X0;
+        X_out[3 * r + 1] = X1;
+        X_out[3 * r + 2] = X2;
+        for (int e = 0; e < n_ext; ++e) ext_cost_out[r * n_ext + e] = ext_cost[a * n_ext + e];
+        int32_t kept = 0;
+#pragma unroll
+        for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+            if (c < n_cams) {
+                const int32_t v = views[a * n_cams + c];
+                const int64_t o = r * n_cams + c;
+                views_out[o] = v;
+                if (v >= 0) {
+                    ++kept;
+                    const int64_t row = co[c] + v;
+                    double cx, cy;
+                    if (VEC) {
+                        reinterpret_cast<int4 *>(boxes_out)[o] = reinterpret_cast<const int4 *>(boxes)[row];
+                        const double2 p = reinterpret_cast<const double2 *>(pts)[row];
+                        reinterpret_cast<double2 *>(cent_out)[o] = p;
+                        cx = p.x;
+                        cy = p.y;
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = boxes[4 * row + q];
+                        cx = pts[2 * row];
+                        cy = pts[2 * row + 1];
+                        cent_out[2 * o] = cx;
+                        cent_out[2 * o + 1] = cy;
+                    }
+                    const double *p = P + 12 * c;
+                    const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
+                    const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
+                    const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
+                    const double du = h0 / h2 - cx, dv = h1 / h2 - cy;
+                    reproj_out[o] = sqrt(du * du + dv * dv);
+                } else {
+                    if (VEC) {
+                        reinterpret_cast<int4 *>(boxes_out)[o] = make_int4(-1, -1, -1, -1);
+                        reinterpret_cast<double2 *>(cent_out)[o] = make_double2(qnan, qnan);
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = -1;
+                        cent_out[2 * o] = qnan;
+                        cent_out[2 * o + 1] = qnan;
+                    }
+                    reproj_out[o] = qnan;
+                }
+            }
+        }
+        nviews_out[r] = kept;
+    }
+}
+
 // ------------------------------------------------- rig matrices ----
 // compute_fundamental_matrix (camera_utils.py:23-46) for every (capture, pair)
 // and P = K @ RT[:3] (process_pose.py:91) for every (capture, camera): one
@@ -701,6 +797,67 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
             cam_offs_dev, n_scenes, scene_base, scene_out_dev, match_out_dev, cost_out_dev, X_out_dev,
             boxes_out_dev, cent_out_dev);
     return mvm_check_launch("compact_matches_kernel");
+}
+
+int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
+                              const float *ext_cost_dev, const double *X_dev, const int32_t *count_dev,
+                              const int64_t *seg_offs_dev, const double *pts_dev,
+                              const int32_t *boxes_dev, const int64_t *cam_offs_dev,
+                              const double *proj_dev, int32_t n_scenes, int32_t n_cams,
+                              int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
+                              int32_t *views_out_dev, int32_t *n_views_out_dev, float *cost_out_dev,
+                              float *ext_cost_out_dev, double *X_out_dev, int32_t *boxes_out_dev,
+                              double *cent_out_dev, double *reproj_out_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    const bool ext = n_cams > 3;         // no extra view: the [cap, 0] arrays may be NULL
+    const struct {
+        const void *p;
+        const char *name;
+    } args[] = {{views_dev, "views_dev"},
+                {cost_dev, "cost_dev"},
+                {ext ? (const void *)ext_cost_dev : (const void *)views_dev, "ext_cost_dev"},
+                {X_dev, "X_dev"},
+                {count_dev, "count_dev"},
+                {seg_offs_dev, "seg_offs_dev"},
+                {pts_dev, "pts_dev"},
+                {boxes_dev, "boxes_dev"},
+                {cam_offs_dev, "cam_offs_dev"},
+                {proj_dev, "proj_dev"},
+                {dense_offs_dev, "dense_offs_dev"},
+                {scene_out_dev, "scene_out_dev"},
+                {views_out_dev, "views_out_dev"},
+                {n_views_out_dev, "n_views_out_dev"},
+                {cost_out_dev, "cost_out_dev"},
+                {ext ? (const void *)ext_cost_out_dev : (const void *)views_dev, "ext_cost_out_dev"},
+                {X_out_dev, "X_out_dev"},
+                {boxes_out_dev, "boxes_out_dev"},
+                {cent_out_dev, "cent_out_dev"},
+                {reproj_out_dev, "reproj_out_dev"}};
+    for (const auto &a : args)
+        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
+    const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
+    const bool vec = ((reinterpret_cast<uintptr_t>(pts_dev) | reinterpret_cast<uintptr_t>(boxes_dev) |
+                       reinterpret_cast<uintptr_t>(boxes_out_dev) |
+                       reinterpret_cast<uintptr_t>(cent_out_dev)) & 15) == 0;
+    if (vec)
+        compact_matches_views_kernel<true><<<grid, kCompactThreads, 0, s>>>(
+            views_dev, cost_dev, ext_cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev,
+            boxes_dev, cam_offs_dev, proj_dev, n_scenes, n_cams, scene_base, scene_out_dev,
+            views_out_dev, n_views_out_dev, cost_out_dev, ext_cost_out_dev, X_out_dev, boxes_out_dev,
+            cent_out_dev, reproj_out_dev);
+    else
+        compact_matches_views_kernel<false><<<grid, kCompactThreads, 0, s>>>(
+            views_dev, cost_dev, ext_cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev,
+            boxes_dev, cam_offs_dev, proj_dev, n_scenes, n_cams, scene_base, scene_out_dev,
+            views_out_dev, n_views_out_dev, cost_out_dev, ext_cost_out_dev, X_out_dev, boxes_out_dev,
+            cent_out_dev, reproj_out_dev);
+    return mvm_check_launch("compact_matches_views_kernel");
 }
 
 int mvm_pack_detections(const float *boxes_dev, const float *conf_dev, const float *cls_dev,

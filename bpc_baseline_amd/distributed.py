@@ -219,8 +219,11 @@ def gather_tables(env: DistEnv, table, n_captures: int):
 
     Rank r holds the table of its ``n_captures`` captures -- a contiguous
     range, in rank order -- with scene ids counted from 0 (``table()``'s
-    default).  One all_gather of (rows, captures) per rank sizes everything;
-    then the per-capture counts and each field are gathered to rank 0, padded
+    default).  One all_gather of (rows, captures, n_cams, optional fields)
+    per rank sizes everything and fixes the field set (``table.fields()``:
+    the views / n_views / ext_cost / reproj of a C-camera or ``reproj=True``
+    table travel too); ranks that disagree on it all raise ``ValueError``.
+    Then the per-capture counts and each field are gathered to rank 0, padded
     to the largest shard and trimmed there: over the default group when it is
     RCCL, on host memory for gloo (as ``gather_rows``).  A field no rank has
     a row of is not exchanged; every rank skips it alike, so a rank with no
@@ -238,11 +241,19 @@ def gather_tables(env: DistEnv, table, n_captures: int):
     on_host = env.backend == "gloo"
     dev = torch.device("cpu") if on_host else env.device
     n_rows = int(table.scene.shape[0])
-    mine = torch.tensor([n_rows, n_captures], dtype=torch.int64, device=dev)
+    names = table.fields()
+    # which optional fields the table holds, reproj among them, as bits
+    mask = sum(1 << i for i, k in enumerate(MatchTable.VIEW_FIELDS) if k in names)
+    mine = torch.tensor([n_rows, n_captures, table.n_cams, mask], dtype=torch.int64, device=dev)
     sizes = [torch.zeros_like(mine) for _ in range(env.world)]
     dist.all_gather(sizes, mine)
     sizes = torch.stack(sizes).cpu().numpy()
     rows, caps = sizes[:, 0], sizes[:, 1]
+    # the field set follows from (n_cams, has reproj): every rank sees every
+    # rank's pair and raises alike, before any further collective
+    if len({(int(c), int(f)) for c, f in sizes[:, 2:]}) != 1:
+        raise ValueError("gather_tables: the ranks' tables differ in (n_cams, optional fields): "
+                         f"{[(int(c), int(f)) for c, f in sizes[:, 2:]]}")
 
     def gather(t: torch.Tensor, lens: np.ndarray) -> Optional[torch.Tensor]:
         # rows of t ([n, ...]) from every rank, n = lens[rank]
@@ -257,7 +268,7 @@ def gather_tables(env: DistEnv, table, n_captures: int):
         return torch.cat([b[:int(n)] for b, n in zip(bufs, lens)]) if env.is_root else None
 
     got_counts = gather(torch.from_numpy(counts), caps)
-    fields = {k: gather(getattr(table, k), rows) for k in MatchTable.FIELDS}
+    fields = {k: gather(getattr(table, k), rows) for k in names}
     if not env.is_root:
         return None
     first = np.concatenate([[0], np.cumsum(caps)[:-1]])       # each rank's first global capture
@@ -265,7 +276,7 @@ def gather_tables(env: DistEnv, table, n_captures: int):
     fields["scene"] = fields["scene"] + shift
     offs = np.zeros(int(caps.sum()) + 1, np.int64)
     np.cumsum(got_counts.cpu().numpy(), out=offs[1:])
-    return MatchTable(offs=offs, **fields)
+    return MatchTable(offs=offs, n_cams=table.n_cams, **fields)
 
 
 def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
@@ -275,7 +286,10 @@ def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
     ``shard_range`` makes such ranges), runs the device chain on it -- not at
     all when its shard is empty --, compacts the result into a ``MatchTable``
     and the tables are gathered to rank 0 (``gather_tables``).  ``kw`` goes to
-    ``match_captures`` (``keep_cube``, the thresholds, ``F``, ``proj``, ...).
+    ``match_captures`` (``keep_cube``, the thresholds, ``F``, ``proj``,
+    ``n_cams``, ...); ``reproj`` in it goes to ``MatchBatch.table`` instead
+    (True: a three-camera table with reprojection residuals; a table of
+    n_cams > 3 always has them).
     ``split``: a dict that receives this rank's seconds in "chain", "table"
     and "gather" (synchronising after each, so only for measurements).
     -> the ``MatchTable`` of all captures on rank 0, None elsewhere."""
@@ -292,13 +306,20 @@ def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
             split[name] = split.get(name, 0.0) + now - clock[0]
             clock[0] = now
 
+    C = int(kw.get("n_cams", 3))
+    reproj = kw.pop("reproj", None)
+    if not 3 <= C <= 8:
+        raise ValueError(f"n_cams: expected 3..8, got {C}")
     n_img = int(img_offs.numel()) - 1
-    if n_img % 3:
-        raise ValueError("img_offs must describe 3 images per capture")
-    S = n_img // 3
+    if n_img % C:
+        raise ValueError(f"img_offs must describe {C} images per capture")
+    S = n_img // C
     batch = match_captures(boxes, conf, cls, img_offs, Ks, RTs, **kw) if S else None
     mark("chain")
-    table = batch.table() if S else MatchTable.empty(dev)
+    # a rank without captures builds the empty table of the same fields from
+    # its own keywords, so it takes part in every collective of the gather
+    reproj = C > 3 or bool(reproj)      # the only table a C-camera batch has
+    table = batch.table(reproj=reproj) if S else MatchTable.empty(dev, n_cams=C, reproj=reproj)
     mark("table")
     out = gather_tables(env, table, S)
     mark("gather")

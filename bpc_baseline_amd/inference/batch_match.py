@@ -87,6 +87,9 @@ class MatchBatch:
     views: Optional[torch.Tensor] = None          # int32 [cap, C]
     ext_cost: Optional[torch.Tensor] = None       # float32 [cap, C - 3]
     n_cams: int = 3
+    # the projection matrices X was triangulated with, all C cameras (what
+    # the table's reprojection residuals are measured against)
+    proj: Optional[torch.Tensor] = None           # float64 [S, C, 3, 4]
 
     def host(self) -> dict:
         """One D2H copy of everything ``predictions`` reads."""
@@ -114,26 +117,47 @@ class MatchBatch:
         rows = self.cam_offs[3 * s:3 * s + 3][None, :] + h["match"][o:o + n].astype(np.int64)
         return [(h["boxes"][rows[q]], h["pts"][rows[q]], h["X"][o + q]) for q in range(n)]
 
-    def table(self, scene_base: int = 0) -> "MatchTable":
+    def table(self, scene_base: int = 0, reproj: Optional[bool] = None) -> "MatchTable":
         """The batch as a dense ``MatchTable`` (mvm_compact_matches): the
         ``count.sum()`` matches in consecutive rows, each with its boxes and
         centroids, scene ids starting at ``scene_base``.  No host sync: the
-        row count is ``count``, already on the host."""
-        if self.n_cams > 3:
-            raise NotImplementedError("MatchTable rows hold three views; a batch of "
-                                      f"n_cams={self.n_cams} has no table yet")
+        row count is ``count``, already on the host.
+
+        ``reproj=True`` goes through mvm_compact_matches_views: rows over all
+        C view slots (``views`` / ``n_views`` / ``ext_cost``) with ``reproj``,
+        the reprojection residual of X in every kept view against ``proj``
+        (DESIGN §3.12).  A three-camera table so made holds the six fields of
+        the plain one bit for bit.  Needs the batch's ``proj``.  That is the
+        only table a batch of n_cams > 3 has: the plain rows hold three
+        views, so without ``reproj=True`` such a batch raises
+        ``NotImplementedError`` as it always did."""
+        C = self.n_cams
+        with_views = bool(reproj)
+        if C > 3 and not with_views:
+            raise NotImplementedError("MatchTable rows without reproj hold three views; a batch of "
+                                      f"n_cams={C} has its table as table(reproj=True)")
+        if with_views and self.proj is None:
+            raise ValueError("the reprojection residuals need the batch's proj (match_captures sets it)")
         S = int(self.count.size)
         offs = np.zeros(S + 1, np.int64)
         np.cumsum(self.count, out=offs[1:])
         n = int(offs[-1])
         dev = self.match.device
         if n == 0:
-            return MatchTable.empty(dev, offs)
+            return MatchTable.empty(dev, offs, n_cams=C, reproj=with_views)
         seg, cam, cnt = self.offs_dev, self.cam_offs_dev, self.count_dev
         if seg is None or cam is None:
             seg, cam = ops._h2d_int64([self.offs, self.cam_offs], dev)
         if cnt is None:
             cnt = torch.from_numpy(np.ascontiguousarray(self.count, np.int32)).to(dev)
+        if with_views:
+            views = self.views if C > 3 else self.match
+            _, scene, views, n_views, cost, ext, X, boxes, cent, rep = ops.compact_matches_views(
+                views, self.cost, self.ext_cost if C > 3 else None, self.X, cnt, seg, self.pts,
+                self.boxes, cam, self.proj.reshape(S, C, 3, 4), scene_base)
+            return MatchTable(scene=scene[:n], match=views[:n, :3], cost=cost[:n], X=X[:n],
+                              boxes=boxes[:n], centroids=cent[:n], offs=offs, views=views[:n],
+                              n_views=n_views[:n], ext_cost=ext[:n], reproj=rep[:n], n_cams=C)
         _, scene, match, cost, X, boxes, cent = ops.compact_matches(
             self.match, self.cost, self.X, cnt, seg, self.pts, self.boxes, cam, scene_base)
         return MatchTable(scene=scene[:n], match=match[:n], cost=cost[:n], X=X[:n], boxes=boxes[:n],
@@ -151,33 +175,73 @@ class MatchTable:
     match: torch.Tensor          # int32 [n, 3]     (i, j, k)
     cost: torch.Tensor           # float32 [n]
     X: torch.Tensor              # float64 [n, 3]   triangulated centre (PosePrediction.t)
-    boxes: torch.Tensor          # int32 [n, 3, 4]  the three views' boxes
-    centroids: torch.Tensor      # float64 [n, 3, 2]
+    boxes: torch.Tensor          # int32 [n, C, 4]  the views' boxes (C = n_cams)
+    centroids: torch.Tensor      # float64 [n, C, 2]
     offs: np.ndarray             # int64 [S + 1]    host
+    # a table made by mvm_compact_matches_views (a batch of n_cams > 3, or
+    # table(reproj=True)): the detection of every view slot, -1 where an extra
+    # view has none (its box is then -1, its centroid and residual NaN;
+    # match == views[:, :3]), and the reprojection residual of X per view
+    views: Optional[torch.Tensor] = None      # int32 [n, C]
+    n_views: Optional[torch.Tensor] = None    # int32 [n]        views >= 0 per row
+    ext_cost: Optional[torch.Tensor] = None   # float32 [n, C - 3]
+    reproj: Optional[torch.Tensor] = None     # float64 [n, C]   pixels
+    n_cams: int = 3
 
     FIELDS = ("scene", "match", "cost", "X", "boxes", "centroids")
+    VIEW_FIELDS = ("views", "n_views", "ext_cost", "reproj")
+
+    def fields(self) -> tuple:
+        """The names of the row fields this table holds: ``FIELDS``, then
+        those of ``VIEW_FIELDS`` that are set."""
+        return self.FIELDS + tuple(k for k in self.VIEW_FIELDS if getattr(self, k) is not None)
 
     @classmethod
-    def empty(cls, device, offs: Optional[np.ndarray] = None) -> "MatchTable":
+    def empty(cls, device, offs: Optional[np.ndarray] = None, n_cams: int = 3,
+              reproj: bool = False) -> "MatchTable":
         """A table of no rows (``offs``: all zero, one entry per capture + 1;
-        default no captures)."""
+        default no captures), of the shapes ``MatchBatch.table(reproj=reproj)``
+        gives a batch of ``n_cams`` cameras."""
+        C = int(n_cams)
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        extra = {}
+        if C > 3 or reproj:
+            extra = dict(views=e((0, C), torch.int32), n_views=e(0, torch.int32),
+                         ext_cost=e((0, C - 3), torch.float32), reproj=e((0, C), torch.float64))
         return cls(scene=e(0, torch.int32), match=e((0, 3), torch.int32), cost=e(0, torch.float32),
-                   X=e((0, 3), torch.float64), boxes=e((0, 3, 4), torch.int32),
-                   centroids=e((0, 3, 2), torch.float64),
-                   offs=np.zeros(1, np.int64) if offs is None else offs)
+                   X=e((0, 3), torch.float64), boxes=e((0, C, 4), torch.int32),
+                   centroids=e((0, C, 2), torch.float64),
+                   offs=np.zeros(1, np.int64) if offs is None else offs, n_cams=C, **extra)
 
     def host(self) -> dict:
         """One D2H copy of the n rows."""
         if not hasattr(self, "_host"):
-            self._host = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+            self._host = {k: getattr(self, k).cpu().numpy() for k in self.fields()}
         return self._host
 
     def predictions(self, s: int) -> List[tuple]:
         """Exactly ``MatchBatch.predictions(s)``: (boxes int32 [3, 4],
-        centroids f64 [3, 2], t f64 [3]) per match of capture s."""
+        centroids f64 [3, 2], t f64 [3]) per match of capture s; for
+        n_cams > 3 (boxes [V, 4], centroids [V, 2], t, cams int64 [V]) over
+        the row's V kept views, cams ascending."""
         h = self.host()
-        return [(h["boxes"][r], h["centroids"][r], h["X"][r])
+        rows = range(int(self.offs[s]), int(self.offs[s + 1]))
+        if self.n_cams > 3:
+            out = []
+            for r in rows:
+                cams = np.nonzero(h["views"][r] >= 0)[0]
+                out.append((h["boxes"][r][cams], h["centroids"][r][cams], h["X"][r], cams))
+            return out
+        return [(h["boxes"][r], h["centroids"][r], h["X"][r]) for r in rows]
+
+    def reprojection(self, s: int) -> List[np.ndarray]:
+        """Per match of capture s, the reprojection residual (pixels, f64 [V])
+        of its X in each view it kept, in the order of ``predictions(s)``'s
+        cams.  Needs a table with ``reproj``."""
+        if self.reproj is None:
+            raise ValueError("this table holds no reprojection residuals (table(reproj=True))")
+        h = self.host()
+        return [h["reproj"][r][h["views"][r] >= 0]
                 for r in range(int(self.offs[s]), int(self.offs[s + 1]))]
 
 
@@ -224,6 +288,10 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     triangulated over all the views it kept.  The result has
     ``views`` / ``ext_cost`` / ``n_cams`` set; matches, costs and order are
     those of the three cameras alone.
+
+    The result keeps ``proj`` (device, [S, C, 3, 4], all C cameras), computed
+    here or passed in: what ``MatchBatch.table`` measures the reprojection
+    residuals against.
     """
     n_cams = int(n_cams)
     if not 3 <= n_cams <= 8:
@@ -345,11 +413,11 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
         return MatchBatch(match=match, cost=cost, X=X, count=count_h, offs=out_offs_host, pts=full[0],
                           boxes=boxes_int, cam_offs=full[2], cube=cube if keep_cube else None,
                           offs_dev=out_offs, count_dev=count, cam_offs_dev=full[1], views=views,
-                          ext_cost=ext_cost, n_cams=C)
+                          ext_cost=ext_cost, n_cams=C, proj=full[5].reshape(S, C, 3, 4))
     return MatchBatch(match=match, cost=cost, X=X, count=count_h,
                       offs=out_offs_host, pts=pts, boxes=boxes_int, cam_offs=cam_offs_host,
                       cube=cube if keep_cube else None, offs_dev=out_offs, count_dev=count,
-                      cam_offs_dev=cam_offs)
+                      cam_offs_dev=cam_offs, proj=proj_dev.reshape(S, 3, 3, 4))
 
 
 def _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C, threshold, mark):

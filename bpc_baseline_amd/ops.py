@@ -37,7 +37,7 @@ __all__ = [
     "pack_detections", "triangulate_dlt", "select_triangulate",
     "triplet_minima", "linear_sum_assignment_resid", "select_triangulate_resid",
     "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats", "compact_matches",
-    "rig_matrices", "extend_costs", "extend_select_triangulate",
+    "rig_matrices", "extend_costs", "extend_select_triangulate", "compact_matches_views",
 ]
 
 
@@ -520,6 +520,63 @@ def compact_matches_out(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, s
 @compact_matches_out.register_fake
 def _(match, cost, X, count, seg_offs, pts, boxes, cam_offs, scene_base, dense_offs, scene_out,
       match_out, cost_out, X_out, boxes_out, cent_out):
+    return None
+
+
+@torch.library.custom_op("mvmatch::compact_matches_views_out",
+                         mutates_args=("dense_offs", "scene_out", "views_out", "n_views_out", "cost_out",
+                                       "ext_cost_out", "X_out", "boxes_out", "cent_out", "reproj_out"))
+def compact_matches_views_out(views: Tensor, cost: Tensor, ext_cost: Tensor, X: Tensor, count: Tensor,
+                              seg_offs: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tensor,
+                              proj: Tensor, scene_base: int, dense_offs: Tensor, scene_out: Tensor,
+                              views_out: Tensor, n_views_out: Tensor, cost_out: Tensor,
+                              ext_cost_out: Tensor, X_out: Tensor, boxes_out: Tensor, cent_out: Tensor,
+                              reproj_out: Tensor) -> None:
+    """The matches of a C-camera batch as dense, self-contained rows with the
+    reprojection residual of every kept view (mvm_compact_matches_views).
+    ``views`` [cap, C] gives C; outputs hold ``cap`` rows."""
+    dev = views.device
+    if dev.type != "cuda":
+        raise ValueError("views must be a GPU tensor (the table has no CPU path)")
+    n_scenes = count.numel()
+    if views.dim() != 2 or not 3 <= views.shape[1] <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"views must be [cap, C], 3 <= C <= {_native.MVM_MAX_CAMS}")
+    cap, C = int(views.shape[0]), int(views.shape[1])
+    for t, name, dt, numel in ((views, "views", torch.int32, C * cap), (cost, "cost", torch.float32, cap),
+                               (ext_cost, "ext_cost", torch.float32, (C - 3) * cap),
+                               (X, "X", torch.float64, 3 * cap), (count, "count", torch.int32, n_scenes),
+                               (seg_offs, "seg_offs", torch.int64, n_scenes + 1),
+                               (pts, "pts", torch.float64, 0), (boxes, "boxes", torch.int32, 0),
+                               (cam_offs, "cam_offs", torch.int64, C * n_scenes + 1),
+                               (proj, "proj", torch.float64, 12 * C * n_scenes),
+                               (dense_offs, "dense_offs", torch.int64, n_scenes + 1),
+                               (scene_out, "scene_out", torch.int32, cap),
+                               (views_out, "views_out", torch.int32, C * cap),
+                               (n_views_out, "n_views_out", torch.int32, cap),
+                               (cost_out, "cost_out", torch.float32, cap),
+                               (ext_cost_out, "ext_cost_out", torch.float32, (C - 3) * cap),
+                               (X_out, "X_out", torch.float64, 3 * cap),
+                               (boxes_out, "boxes_out", torch.int32, 4 * C * cap),
+                               (cent_out, "cent_out", torch.float64, 2 * C * cap),
+                               (reproj_out, "reproj_out", torch.float64, C * cap)):
+        _require(t, name, dt, dev)
+        if numel and t.numel() != numel and name in ("seg_offs", "cam_offs", "dense_offs", "proj"):
+            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+        if t.numel() < numel:
+            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
+    if boxes.numel() != 2 * pts.numel():
+        raise ValueError("pts [n, 2] and boxes [n, 4] differ in rows")
+    st = _native.load().mvm_compact_matches_views(
+        _p(views), _p(cost), _p(ext_cost), _p(X), _p(count), _p(seg_offs), _p(pts), _p(boxes),
+        _p(cam_offs), _p(proj), n_scenes, C, int(scene_base), _p(dense_offs), _p(scene_out),
+        _p(views_out), _p(n_views_out), _p(cost_out), _p(ext_cost_out), _p(X_out), _p(boxes_out),
+        _p(cent_out), _p(reproj_out), _stream(views))
+    _native.check("mvm_compact_matches_views", st)
+
+
+@compact_matches_views_out.register_fake
+def _(views, cost, ext_cost, X, count, seg_offs, pts, boxes, cam_offs, proj, scene_base, dense_offs,
+      scene_out, views_out, n_views_out, cost_out, ext_cost_out, X_out, boxes_out, cent_out, reproj_out):
     return None
 
 
@@ -1151,6 +1208,37 @@ def compact_matches(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_o
                                               X_out, boxes_out, cent_out)
     return (dense_offs, scene[:cap], match_out[:cap], cost_out[:cap], X_out[:cap], boxes_out[:cap],
             cent_out[:cap])
+
+
+def compact_matches_views(views: Tensor, cost: Tensor, ext_cost: Optional[Tensor], X: Tensor,
+                          count: Tensor, seg_offs: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tensor,
+                          proj: Tensor, scene_base: int = 0):
+    """The dense match table of a C-camera result with its reprojection
+    residuals (device; mvm_compact_matches_views): ``compact_matches`` over the
+    C view slots of ``views`` int32 [cap, C] (a three-camera result: its
+    ``match``; ``ext_cost`` f32 [cap, C-3], None for C == 3), ``proj`` f64
+    [S, C, 3, 4].  A slot of -1 gets a box of -1 and NaN centroid / residual.
+    -> (dense_offs i64 [S+1], scene i32 [cap], views i32 [cap, C], n_views i32
+    [cap], cost f32 [cap], ext_cost f32 [cap, C-3], X f64 [cap, 3], boxes i32
+    [cap, C, 4], centroids f64 [cap, C, 2], reproj f64 [cap, C]); rows at and
+    beyond ``dense_offs[S]`` (= count.sum()) are unused capacity."""
+    dev = views.device
+    cap, C = int(views.shape[0]), int(views.shape[1])
+    n_scenes = int(count.numel())
+    if ext_cost is None:
+        ext_cost = torch.empty((cap, C - 3), dtype=torch.float32, device=dev)
+    dense_offs = torch.zeros(n_scenes + 1, dtype=torch.int64, device=dev)
+    rows = max(cap, 1)
+    e = lambda shape, dt: torch.empty((rows,) + shape, dtype=dt, device=dev)
+    outs = (e((), torch.int32), e((C,), torch.int32), e((), torch.int32), e((), torch.float32),
+            e((C - 3,), torch.float32), e((3,), torch.float64), e((C, 4), torch.int32),
+            e((C, 2), torch.float64), e((C,), torch.float64))
+    # no row to copy: every count is 0 and the offsets stay 0; nothing is launched
+    if n_scenes and cap and pts.numel():
+        torch.ops.mvmatch.compact_matches_views_out(views, cost, ext_cost, X, count, seg_offs, pts, boxes,
+                                                    cam_offs, proj.contiguous(), int(scene_base),
+                                                    dense_offs, *outs)
+    return (dense_offs,) + tuple(o[:cap] for o in outs)
 
 
 def extend_costs(pts: Tensor, cam_offs: Tensor, F_ext: Tensor, match: Tensor, match_offs: Tensor,

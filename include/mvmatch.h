@@ -44,6 +44,8 @@ extern "C" {
                                   signature or struct changed) */
 #define MVM_HAS_EXTEND 1 /* mvm_extend_costs, mvm_extend_select_triangulate: additions to
                             ABI 8 (no existing signature or struct changed) */
+#define MVM_HAS_VIEW_TABLE 1 /* mvm_compact_matches_views: an addition to ABI 8 (no existing
+                                signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -622,6 +624,54 @@ int mvm_extend_select_triangulate(const float *E_dev, const int64_t *ext_offs_de
                                   const double *proj_dev, int32_t n_scenes, int32_t n_cams,
                                   double threshold, int32_t *views_dev, float *ext_cost_dev,
                                   double *X_dev, mvm_stream_t stream);
+
+/*
+ * The dense match table of a C-camera batch, 3 <= C <= MVM_MAX_CAMS, with the
+ * reprojection residual of every kept view (an addition to ABI 8, announced
+ * by MVM_HAS_VIEW_TABLE): mvm_compact_matches over the C view slots.  Inputs
+ * (read only, not aliasing the outputs): views_dev int32 [cap, C], cost_dev
+ * f32 [cap], ext_cost_dev f32 [cap, C-3], X_dev f64 [cap, 3], count_dev int32
+ * [S] under seg_offs_dev int64 [S+1], as mvm_select_triangulate(_resid) and
+ * mvm_extend_select_triangulate left them (C == 3: match_dev is views_dev, and
+ * ext_cost_dev / ext_cost_out_dev, arrays of no element, may be NULL);
+ * pts_dev f64 [n, 2], boxes_dev int32 [n, 4], cam_offs_dev int64 [C*S + 1]:
+ * the C-camera CSR of mvm_pack_detections; proj_dev f64 [S, C, 3, 4].
+ * Preconditions (not checked): 0 <= count[s] <= seg_offs[s+1] - seg_offs[s],
+ * and every views entry is -1 or a detection of its view.
+ * Outputs, each with room for seg_offs[S] rows: dense_offs_dev int64 [S+1] =
+ * the exclusive prefix sum of count; for match w of capture s, at row
+ * r = dense_offs[s] + w, with v_c = views[seg_offs[s] + w][c]:
+ *   scene_out_dev[r]     int32         scene_base + s
+ *   views_out_dev[r]     int32 [C]     the v_c (-1: no detection in that view)
+ *   n_views_out_dev[r]   int32         the number of v_c >= 0
+ *   cost_out_dev[r]      f32           copied
+ *   ext_cost_out_dev[r]  f32 [C-3]     copied
+ *   X_out_dev[r]         f64 [3]       copied
+ *   boxes_out_dev[r]     int32 [C, 4]  boxes[cam_offs[C*s + c] + v_c], or
+ *                                      (-1, -1, -1, -1) where v_c < 0
+ *   cent_out_dev[r]      f64 [C, 2]    the same rows of pts, or quiet NaN
+ *   reproj_out_dev[r]    f64 [C]       the residual below, or quiet NaN
+ * Reprojection residual of view c, with P = proj[s][c], X the row's X and
+ * (cx, cy) its centroid in that view -- fp64, in exactly this order, every
+ * product and sum rounded on its own (no FMA), IEEE division and square root:
+ *   h_q = ((P[q][0]*X0 + P[q][1]*X1) + P[q][2]*X2) + P[q][3]      q = 0, 1, 2
+ *   u = h_0 / h_2;  v = h_1 / h_2;  du = u - cx;  dv = v - cy
+ *   reproj = sqrt(du*du + dv*dv)
+ * (h_2 == 0 gives inf or NaN as IEEE does.)  Copied values are bit-exact;
+ * rows at and beyond dense_offs[S] are not written.  Two launches (the prefix
+ * sum, the copy) on `stream`, no allocation, copy or synchronisation;
+ * n_scenes == 0 launches nothing.  A NULL pointer other than the two optional
+ * ones, or n_cams outside 3..MVM_MAX_CAMS, is refused before any launch.
+ */
+int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
+                              const float *ext_cost_dev, const double *X_dev, const int32_t *count_dev,
+                              const int64_t *seg_offs_dev, const double *pts_dev,
+                              const int32_t *boxes_dev, const int64_t *cam_offs_dev,
+                              const double *proj_dev, int32_t n_scenes, int32_t n_cams,
+                              int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
+                              int32_t *views_out_dev, int32_t *n_views_out_dev, float *cost_out_dev,
+                              float *ext_cost_out_dev, double *X_out_dev, int32_t *boxes_out_dev,
+                              double *cent_out_dev, double *reproj_out_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory
