@@ -53,6 +53,12 @@ int mvm_check_launch(const char *what) {
     return MVM_OK;
 }
 
+int mvm_require_ptrs(std::initializer_list<mvm_named_ptr> args) {
+    for (const auto &a : args)
+        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    return MVM_OK;
+}
+
 int mvm_resolve_options(const mvm_options *in, mvm_options &out) {
     mvm_options_init(&out);
     if (!in) return MVM_OK;

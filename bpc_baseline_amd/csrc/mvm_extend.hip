@@ -187,15 +187,11 @@ int mvm_extend_costs(const double *pts_dev, const int64_t *cam_offs_dev, const d
     if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
     if (n_scenes == 0 || n_cams == 3 || max_rows == 0) return MVM_OK;
-    const struct {
-        const void *p;
-        const char *name;
-    } args[] = {{pts_dev, "pts_dev"},           {cam_offs_dev, "cam_offs_dev"},
-                {F_ext_dev, "F_ext_dev"},       {match_dev, "match_dev"},
-                {match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
-                {ext_offs_dev, "ext_offs_dev"}, {E_dev, "E_dev"}};
-    for (const auto &a : args)
-        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    if (const int st = mvm_require_ptrs({{pts_dev, "pts_dev"},               {cam_offs_dev, "cam_offs_dev"},
+                                         {F_ext_dev, "F_ext_dev"},           {match_dev, "match_dev"},
+                                         {match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
+                                         {ext_offs_dev, "ext_offs_dev"},     {E_dev, "E_dev"}}))
+        return st;
     const int64_t row_blocks = ((int64_t)max_rows + kExtRows - 1) / kExtRows;
     const int64_t grid = (int64_t)n_scenes * (n_cams - kExtAnchors) * row_blocks;
     if (grid > kMaxGridBlocks)

@@ -7,12 +7,21 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "mvmatch.h"
 
 int mvm_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void mvm_set_error(const char *msg);
 void mvm_clear_error();
 int mvm_check_launch(const char *what);
+// MVM_OK, or MVM_ERR_INVALID_ARGUMENT with "null pointer: <name>" recorded for
+// the first NULL of {pointer, name}, ...
+struct mvm_named_ptr {
+    const void *p;
+    const char *name;
+};
+int mvm_require_ptrs(std::initializer_list<mvm_named_ptr> args);
 // *in (NULL = defaults) -> out, every field present; MVM_OK or an error code
 int mvm_resolve_options(const mvm_options *in, mvm_options &out);
 // dynamic LDS above 64 KiB needs the kernel's opt-in; MVM_OK or MVM_ERR_HIP

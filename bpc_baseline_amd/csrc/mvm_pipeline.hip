@@ -22,6 +22,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mvmatch.h"
 #include "mvm_device.h"
 #include "mvm_internal.h"
@@ -717,6 +719,23 @@ __global__ __launch_bounds__(kRigThreads) void rig_matrices_kernel(
     }
 }
 
+// ---- host: launch helpers -------------------------------------------------------
+// every pointer on a 16-byte boundary (what the VEC kernels' 16-byte accesses need)
+template <typename... T>
+bool aligned16(const T *...p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// f(std::true_type) or f(std::false_type): a launch written once for both
+// values of a kernel's bool template parameter
+template <typename F>
+void dispatch_bool(bool b, F &&f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -731,13 +750,9 @@ int mvm_rig_matrices(const float *K_dev, const double *RT_dev, const int32_t *pa
         return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [2, %d]", n_cams, MVM_MAX_CAMS);
     if (n_pairs < 1 || n_pairs > MVM_MAX_PAIRS)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "n_pairs=%d outside [1, %d]", n_pairs, MVM_MAX_PAIRS);
-    const struct {
-        const void *p;
-        const char *name;
-    } args[] = {{K_dev, "K_dev"},   {RT_dev, "RT_dev"}, {pair_a, "pair_a"},
-                {pair_b, "pair_b"}, {F_dev, "F_dev"},   {status_dev, "status_dev"}};
-    for (const auto &a : args)
-        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    if (const int st = mvm_require_ptrs({{K_dev, "K_dev"},   {RT_dev, "RT_dev"}, {pair_a, "pair_a"},
+                                         {pair_b, "pair_b"}, {F_dev, "F_dev"},   {status_dev, "status_dev"}}))
+        return st;
     RigPairs pairs{};
     for (int p = 0; p < n_pairs; ++p) {
         if (pair_a[p] < 0 || pair_a[p] >= n_cams || pair_b[p] < 0 || pair_b[p] >= n_cams ||
@@ -767,35 +782,24 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
     mvm_clear_error();
     if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
     if (n_scenes == 0) return MVM_OK;
-    const struct {
-        const void *p;
-        const char *name;
-    } args[] = {{match_dev, "match_dev"},         {cost_dev, "cost_dev"},
-                {X_dev, "X_dev"},                 {count_dev, "count_dev"},
-                {seg_offs_dev, "seg_offs_dev"},   {pts_dev, "pts_dev"},
-                {boxes_dev, "boxes_dev"},         {cam_offs_dev, "cam_offs_dev"},
-                {dense_offs_dev, "dense_offs_dev"}, {scene_out_dev, "scene_out_dev"},
-                {match_out_dev, "match_out_dev"}, {cost_out_dev, "cost_out_dev"},
-                {X_out_dev, "X_out_dev"},         {boxes_out_dev, "boxes_out_dev"},
-                {cent_out_dev, "cent_out_dev"}};
-    for (const auto &a : args)
-        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    if (const int st = mvm_require_ptrs({{match_dev, "match_dev"},         {cost_dev, "cost_dev"},
+                                         {X_dev, "X_dev"},                 {count_dev, "count_dev"},
+                                         {seg_offs_dev, "seg_offs_dev"},   {pts_dev, "pts_dev"},
+                                         {boxes_dev, "boxes_dev"},         {cam_offs_dev, "cam_offs_dev"},
+                                         {dense_offs_dev, "dense_offs_dev"}, {scene_out_dev, "scene_out_dev"},
+                                         {match_out_dev, "match_out_dev"}, {cost_out_dev, "cost_out_dev"},
+                                         {X_out_dev, "X_out_dev"},         {boxes_out_dev, "boxes_out_dev"},
+                                         {cent_out_dev, "cent_out_dev"}}))
+        return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
     const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
-    const bool vec = ((reinterpret_cast<uintptr_t>(pts_dev) | reinterpret_cast<uintptr_t>(boxes_dev) |
-                       reinterpret_cast<uintptr_t>(boxes_out_dev) |
-                       reinterpret_cast<uintptr_t>(cent_out_dev)) & 15) == 0;
-    if (vec)
-        compact_matches_kernel<true><<<grid, kCompactThreads, 0, s>>>(
+    dispatch_bool(aligned16(pts_dev, boxes_dev, boxes_out_dev, cent_out_dev), [&](auto vec) {
+        compact_matches_kernel<decltype(vec)::value><<<grid, kCompactThreads, 0, s>>>(
             match_dev, cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev, boxes_dev,
             cam_offs_dev, n_scenes, scene_base, scene_out_dev, match_out_dev, cost_out_dev, X_out_dev,
             boxes_out_dev, cent_out_dev);
-    else
-        compact_matches_kernel<false><<<grid, kCompactThreads, 0, s>>>(
-            match_dev, cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev, boxes_dev,
-            cam_offs_dev, n_scenes, scene_base, scene_out_dev, match_out_dev, cost_out_dev, X_out_dev,
-            boxes_out_dev, cent_out_dev);
+    });
     return mvm_check_launch("compact_matches_kernel");
 }
 
@@ -814,49 +818,37 @@ int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
     if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
     const bool ext = n_cams > 3;         // no extra view: the [cap, 0] arrays may be NULL
-    const struct {
-        const void *p;
-        const char *name;
-    } args[] = {{views_dev, "views_dev"},
-                {cost_dev, "cost_dev"},
-                {ext ? (const void *)ext_cost_dev : (const void *)views_dev, "ext_cost_dev"},
-                {X_dev, "X_dev"},
-                {count_dev, "count_dev"},
-                {seg_offs_dev, "seg_offs_dev"},
-                {pts_dev, "pts_dev"},
-                {boxes_dev, "boxes_dev"},
-                {cam_offs_dev, "cam_offs_dev"},
-                {proj_dev, "proj_dev"},
-                {dense_offs_dev, "dense_offs_dev"},
-                {scene_out_dev, "scene_out_dev"},
-                {views_out_dev, "views_out_dev"},
-                {n_views_out_dev, "n_views_out_dev"},
-                {cost_out_dev, "cost_out_dev"},
-                {ext ? (const void *)ext_cost_out_dev : (const void *)views_dev, "ext_cost_out_dev"},
-                {X_out_dev, "X_out_dev"},
-                {boxes_out_dev, "boxes_out_dev"},
-                {cent_out_dev, "cent_out_dev"},
-                {reproj_out_dev, "reproj_out_dev"}};
-    for (const auto &a : args)
-        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    if (const int st = mvm_require_ptrs({{views_dev, "views_dev"},
+                                         {cost_dev, "cost_dev"},
+                                         {ext ? (const void *)ext_cost_dev : views_dev, "ext_cost_dev"},
+                                         {X_dev, "X_dev"},
+                                         {count_dev, "count_dev"},
+                                         {seg_offs_dev, "seg_offs_dev"},
+                                         {pts_dev, "pts_dev"},
+                                         {boxes_dev, "boxes_dev"},
+                                         {cam_offs_dev, "cam_offs_dev"},
+                                         {proj_dev, "proj_dev"},
+                                         {dense_offs_dev, "dense_offs_dev"},
+                                         {scene_out_dev, "scene_out_dev"},
+                                         {views_out_dev, "views_out_dev"},
+                                         {n_views_out_dev, "n_views_out_dev"},
+                                         {cost_out_dev, "cost_out_dev"},
+                                         {ext ? (const void *)ext_cost_out_dev : views_dev, "ext_cost_out_dev"},
+                                         {X_out_dev, "X_out_dev"},
+                                         {boxes_out_dev, "boxes_out_dev"},
+                                         {cent_out_dev, "cent_out_dev"},
+                                         {reproj_out_dev, "reproj_out_dev"}}))
+        return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
     const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
-    const bool vec = ((reinterpret_cast<uintptr_t>(pts_dev) | reinterpret_cast<uintptr_t>(boxes_dev) |
-                       reinterpret_cast<uintptr_t>(boxes_out_dev) |
-                       reinterpret_cast<uintptr_t>(cent_out_dev)) & 15) == 0;
-    if (vec)
-        compact_matches_views_kernel<true><<<grid, kCompactThreads, 0, s>>>(
+    dispatch_bool(aligned16(pts_dev, boxes_dev, boxes_out_dev, cent_out_dev), [&](auto vec) {
+        compact_matches_views_kernel<decltype(vec)::value><<<grid, kCompactThreads, 0, s>>>(
             views_dev, cost_dev, ext_cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev,
             boxes_dev, cam_offs_dev, proj_dev, n_scenes, n_cams, scene_base, scene_out_dev,
             views_out_dev, n_views_out_dev, cost_out_dev, ext_cost_out_dev, X_out_dev, boxes_out_dev,
             cent_out_dev, reproj_out_dev);
-    else
-        compact_matches_views_kernel<false><<<grid, kCompactThreads, 0, s>>>(
-            views_dev, cost_dev, ext_cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev,
-            boxes_dev, cam_offs_dev, proj_dev, n_scenes, n_cams, scene_base, scene_out_dev,
-            views_out_dev, n_views_out_dev, cost_out_dev, ext_cost_out_dev, X_out_dev, boxes_out_dev,
-            cent_out_dev, reproj_out_dev);
+    });
     return mvm_check_launch("compact_matches_views_kernel");
 }
 
@@ -937,16 +929,12 @@ int mvm_extend_select_triangulate(const float *E_dev, const int64_t *ext_offs_de
     if (n_scenes == 0 || n_cams == 3) return MVM_OK;
     // E / row_ind / col_ind / pts may be NULL when every extra view or every
     // capture is empty (nothing then reads them)
-    const struct {
-        const void *p;
-        const char *name;
-    } args[] = {{ext_offs_dev, "ext_offs_dev"},     {lsap_out_offs_dev, "lsap_out_offs_dev"},
-                {match_dev, "match_dev"},           {match_offs_dev, "match_offs_dev"},
-                {count_dev, "count_dev"},           {cam_offs_dev, "cam_offs_dev"},
-                {proj_dev, "proj_dev"},             {views_dev, "views_dev"},
-                {ext_cost_dev, "ext_cost_dev"},     {X_dev, "X_dev"}};
-    for (const auto &a : args)
-        if (!a.p) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer: %s", a.name);
+    if (const int st = mvm_require_ptrs({{ext_offs_dev, "ext_offs_dev"}, {lsap_out_offs_dev, "lsap_out_offs_dev"},
+                                         {match_dev, "match_dev"},       {match_offs_dev, "match_offs_dev"},
+                                         {count_dev, "count_dev"},       {cam_offs_dev, "cam_offs_dev"},
+                                         {proj_dev, "proj_dev"},         {views_dev, "views_dev"},
+                                         {ext_cost_dev, "ext_cost_dev"}, {X_dev, "X_dev"}}))
+        return st;
     extend_select_triangulate_kernel<<<n_scenes, kSelThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
         E_dev, ext_offs_dev, lsap_out_offs_dev, row_ind_dev, col_ind_dev, match_dev, match_offs_dev,
         count_dev, pts_dev, cam_offs_dev, proj_dev, threshold, n_cams, views_dev, ext_cost_dev, X_dev);

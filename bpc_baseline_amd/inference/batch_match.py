@@ -29,7 +29,7 @@ from __future__ import annotations
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import Iterable, Iterator, List, Optional, Sequence
+from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -42,15 +42,55 @@ __all__ = ["MatchBatch", "MatchTable", "extension_pairs", "match_capture_stream"
            "projection_matrices", "rig_matrices", "rig_worker_pool"]
 
 
+def _check_n_cams(n_cams) -> int:
+    if not 3 <= int(n_cams) <= 8:
+        raise ValueError(f"n_cams: expected 3..8, got {n_cams}")
+    return int(n_cams)
+
+
+def _check_rig(rig: str) -> None:
+    if rig not in ("host", "device", "auto"):
+        raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
+
+
+def _raise_failed(bad) -> None:
+    """``bad``: per capture, nonzero where an assignment's status was."""
+    raise ValueError(f"assignment failed for captures {np.nonzero(bad)[0][:8].tolist()} "
+                     "(cost matrix contains invalid numeric entries or is infeasible)")
+
+
 def extension_pairs(n_cams: int) -> np.ndarray:
     """The camera pairs whose F ``match_captures(n_cams=C)`` uses, in its
     order -> int32 [3 + 3 (C - 3), 2]: (0,1), (0,2), (1,2) of the three-camera
     chain, then per extra camera d = 3 .. C-1 its pairs with the three anchor
     cameras (0,d), (1,d), (2,d)."""
-    if not 3 <= int(n_cams) <= 8:
-        raise ValueError(f"n_cams: expected 3..8, got {n_cams}")
-    out = [(0, 1), (0, 2), (1, 2)] + [(c, d) for d in range(3, int(n_cams)) for c in range(3)]
+    C = _check_n_cams(n_cams)
+    out = [(0, 1), (0, 2), (1, 2)] + [(c, d) for d in range(3, C) for c in range(3)]
     return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+
+class _Rig(NamedTuple):
+    """The packed detections and camera matrices of a batch of S captures of
+    C cameras, as the device chain reads them."""
+    pts: torch.Tensor            # float64 [n, 2]
+    cam_offs: torch.Tensor       # int64 [C S + 1]  CSR of pts (device)
+    cam_offs_host: np.ndarray    # the same on the host
+    counts: np.ndarray           # int64 [S, C]     detections per view
+    F: torch.Tensor              # float64, flat: 3 + 3 (C - 3) matrices per capture
+    proj: torch.Tensor           # float64 [S, C, 3, 4]
+
+
+class _Chain(NamedTuple):
+    """What the three-camera chain leaves on the device (scene s owns rows
+    ``offs_host[s] : offs_host[s] + count[s]`` of match / cost / X)."""
+    match: torch.Tensor          # int32 [cap, 3]
+    cost: torch.Tensor           # float32 [cap]
+    X: torch.Tensor              # float64 [cap, 3]
+    status: torch.Tensor         # int32 [S]        the assignment's, 0 = solved
+    count: torch.Tensor          # int32 [S]
+    offs_host: np.ndarray        # int64 [S + 1]
+    cube: Optional[torch.Tensor]
+    offs_dev: torch.Tensor       # offs_host on the device
 
 
 def _host_rig(Ks: np.ndarray, RTs: np.ndarray, n_cams: int):
@@ -293,12 +333,8 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     here or passed in: what ``MatchBatch.table`` measures the reprojection
     residuals against.
     """
-    n_cams = int(n_cams)
-    if not 3 <= n_cams <= 8:
-        raise ValueError(f"n_cams: expected 3..8, got {n_cams}")
-    C = n_cams
-    if rig not in ("host", "device", "auto"):
-        raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
+    C = _check_n_cams(n_cams)
+    _check_rig(rig)
     if rig != "host" and (F is not None or proj is not None):
         raise TypeError(f"F / proj cannot be passed with rig={rig!r}: that path computes them")
     dev = boxes.device
@@ -347,7 +383,6 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                 proj = torch.from_numpy(P_h).to(dev)
         mark("F+P host")
     F_dev = F.reshape(-1)
-    proj_dev = proj
 
     # one device -> host copy: the kept counts and the packing status (and the
     # device rig's per-capture status)
@@ -373,67 +408,60 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     np.cumsum(counts_host, out=cam_offs_host[1:])
     mark("counts D2H")
 
-    full = None
+    threshold = float(matching_threshold)
+    full = _Rig(pts, cam_offs, cam_offs_host, counts_host.reshape(S, C), F_dev, proj)
+    three = full
     if C > 3:
         # cameras 0, 1, 2 of every capture as a three-camera batch of its own
         # (centroids, F and P gathered on the device); the existing chain runs
         # on it untouched
-        full = (pts, cam_offs, cam_offs_host, counts_host.reshape(S, C), F_dev, proj_dev)
         rows = np.nonzero(np.repeat(np.arange(S * C) % C < 3, counts_host))[0].astype(np.int64)
-        counts_host = np.ascontiguousarray(counts_host.reshape(S, C)[:, :3]).reshape(-1)
-        cam_offs_host = np.zeros(3 * S + 1, np.int64)
-        np.cumsum(counts_host, out=cam_offs_host[1:])
-        sel, cam_offs = ops._h2d_int64([rows, cam_offs_host], dev)
-        pts = pts.index_select(0, sel) if rows.size else pts[:0]
-        F_dev = F_dev.view(S, n_pairs, 9)[:, :3].reshape(-1)
-        proj_dev = proj_dev.view(S, C, 3, 4)[:, :3].contiguous()
+        c3 = np.ascontiguousarray(full.counts[:, :3])
+        co3 = np.zeros(3 * S + 1, np.int64)
+        np.cumsum(c3.reshape(-1), out=co3[1:])
+        sel, co3_dev = ops._h2d_int64([rows, co3], dev)
+        three = _Rig(pts.index_select(0, sel) if rows.size else pts[:0], co3_dev, co3, c3,
+                     full.F.view(S, n_pairs, 9)[:, :3].reshape(-1),
+                     full.proj.view(S, C, 3, 4)[:, :3].contiguous())
         mark("three-view gather")
-    c3 = counts_host.reshape(S, 3)
-    free = ops.cube_free_scenes(c3) if not keep_cube else np.zeros(S, bool)
+    free = ops.cube_free_scenes(three.counts) if not keep_cube else np.zeros(S, bool)
     if free.all() or not free.any():
-        res = _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, float(matching_threshold),
-                            bool(free.all()) and S > 0, keep_cube, mark)
+        res = _device_chain(three, S, threshold, bool(free.all()) and S > 0, keep_cube, mark)
     else:
         # a mixed batch: the scenes of the candidate-list class without the
         # cube, the others (small views: the dense assignment classes read
         # the cost) with it; each part is a contiguous sub-batch
-        res = _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, float(matching_threshold), free,
-                           mark)
-    match, cost, X, lstat, count, out_offs_host, cube, out_offs = res
+        res = _split_chain(three, S, threshold, free, mark)
     # one device -> host copy: assignment statuses and match counts
-    sc = torch.cat([lstat, count]).cpu().numpy()
+    sc = torch.cat([res.status, res.count]).cpu().numpy()
     bad, count_h = sc[:S], sc[S:]
     if np.any(bad):
-        raise ValueError(f"assignment failed for captures {np.nonzero(bad)[0][:8].tolist()} "
-                         "(cost matrix contains invalid numeric entries or is infeasible)")
+        _raise_failed(bad)
     mark("results D2H")
-    if full is not None:
-        views, ext_cost = _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C,
-                                  float(matching_threshold), mark)
-        return MatchBatch(match=match, cost=cost, X=X, count=count_h, offs=out_offs_host, pts=full[0],
-                          boxes=boxes_int, cam_offs=full[2], cube=cube if keep_cube else None,
-                          offs_dev=out_offs, count_dev=count, cam_offs_dev=full[1], views=views,
-                          ext_cost=ext_cost, n_cams=C, proj=full[5].reshape(S, C, 3, 4))
-    return MatchBatch(match=match, cost=cost, X=X, count=count_h,
-                      offs=out_offs_host, pts=pts, boxes=boxes_int, cam_offs=cam_offs_host,
-                      cube=cube if keep_cube else None, offs_dev=out_offs, count_dev=count,
-                      cam_offs_dev=cam_offs, proj=proj_dev.reshape(S, 3, 3, 4))
+    views = ext_cost = None
+    if C > 3:
+        views, ext_cost = _extend(full, res, count_h, S, C, threshold, mark)
+    return MatchBatch(match=res.match, cost=res.cost, X=res.X, count=count_h, offs=res.offs_host,
+                      pts=full.pts, boxes=boxes_int, cam_offs=full.cam_offs_host,
+                      cube=res.cube if keep_cube else None, offs_dev=res.offs_dev, count_dev=res.count,
+                      cam_offs_dev=full.cam_offs, views=views, ext_cost=ext_cost, n_cams=C,
+                      proj=full.proj.reshape(S, C, 3, 4))
 
 
-def _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C, threshold, mark):
+def _extend(full: _Rig, res: _Chain, count_h, S, C, threshold, mark):
     """The extension of the three-view matches into cameras 3 .. C-1 (DESIGN
     §3.14): cost matrices -> assignment -> threshold + V-view DLT, behind the
-    results copy (``count_h``: the match counts on the host).  ``X`` is
+    results copy (``count_h``: the match counts on the host).  ``res.X`` is
     updated in place.  -> (views int32 [cap, C], ext_cost f32 [cap, C - 3]).
     One device -> host copy: the assignment statuses."""
-    pts, cam_offs, _, counts, F_dev, proj = full
+    pts, cam_offs, match, count, out_offs = full.pts, full.cam_offs, res.match, res.count, res.offs_dev
     dev = pts.device
     n_ext = C - 3
     cap = int(match.shape[0])
     views = torch.empty((cap, C), dtype=torch.int32, device=dev)
     ext_cost = torch.empty((cap, n_ext), dtype=torch.float32, device=dev)
     rows = np.repeat(np.asarray(count_h, np.int64), n_ext)
-    cols = counts[:, 3:].reshape(-1).astype(np.int64)
+    cols = full.counts[:, 3:].reshape(-1).astype(np.int64)
     # every matrix starts on a 16-byte boundary (aligned rows then store 16 bytes a lane)
     ext_offs_host = np.zeros(S * n_ext + 1, np.int64)
     np.cumsum((rows * cols + 3) // 4 * 4, out=ext_offs_host[1:])
@@ -441,7 +469,7 @@ def _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C, thres
     if cap == 0 or max_rows == 0:
         return views, ext_cost
     ext_offs, = ops._h2d_int64([ext_offs_host], dev)
-    F_ext = F_dev.view(S, 3 + 3 * n_ext, 9)[:, 3:].contiguous()
+    F_ext = full.F.view(S, 3 + 3 * n_ext, 9)[:, 3:].contiguous()
     E = ops.extend_costs(pts, cam_offs, F_ext, match, out_offs, count, ext_offs, C, max_rows,
                          size=int(ext_offs_host[-1]))
     mark("extend costs")
@@ -449,24 +477,21 @@ def _extend(full, match, X, count, count_h, out_offs, out_offs_host, S, C, thres
     row_ind, col_ind, lstat = ops.linear_sum_assignment_batched(E, ext_offs[:-1].contiguous(), lplan)
     mark("extend lsap")
     ops.extend_select_triangulate(E, ext_offs, lplan.out_offs, row_ind, col_ind, match, out_offs, count,
-                                  pts, cam_offs, proj, threshold, X, C, out=(views, ext_cost))
+                                  pts, cam_offs, full.proj, threshold, res.X, C, out=(views, ext_cost))
     mark("extend select")
     bad = lstat.cpu().numpy().reshape(S, n_ext).any(axis=1)
     if np.any(bad):
-        raise ValueError(f"assignment failed for captures {np.nonzero(bad)[0][:8].tolist()} "
-                         "(cost matrix contains invalid numeric entries or is infeasible)")
+        _raise_failed(bad)
     mark("extend D2H")
     return views, ext_cost
 
 
-def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, cube_free, keep_cube,
-                  mark):
+def _device_chain(rig: _Rig, S, threshold, cube_free, keep_cube, mark) -> _Chain:
     """Cube (or, cube_free, its 8-row minima + pair residuals) -> assignment ->
-    select/DLT of S scenes whose CSR offsets are ``cam_offs`` (device) /
-    ``cam_offs_host``.  -> (match, cost, X, status, count, out_offs_host, cube or None,
-    out_offs on the device)."""
+    select/DLT of the S three-camera scenes of ``rig``."""
+    pts, cam_offs, F_dev, proj_dev = rig.pts, rig.cam_offs, rig.F, rig.proj
     dev = pts.device
-    plan = ops.TripletPlan(cam_offs_host, S, device=dev)
+    plan = ops.TripletPlan(rig.cam_offs_host, S, device=dev)
     c3 = plan.counts
     mark("cube plan")
     if cube_free:
@@ -483,13 +508,12 @@ def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, c
         match, cost, X, count = ops.select_triangulate_resid(plan, cam_offs, lplan.out_offs, row_ind,
                                                              col_ind, pts, proj_dev, threshold)
         mark("select")
-        return match, cost, X, lstat, count, lplan.out_offs_host, None, lplan.out_offs
+        return _Chain(match, cost, X, lstat, count, lplan.out_offs_host, None, lplan.out_offs)
     # flattened cubes of the candidate-list class: the cube kernel also writes
     # the 8-row minima that class reduces
     bm8 = None
-    lo, hi, sh = ops.sparse_class_bounds()
     nm = c3[:, 0] * c3[:, 1]
-    if S and bool(((nm >= lo) & (nm > 1024) & (nm <= hi) & (c3[:, 2] <= sh) & (nm > c3[:, 2])).any()):
+    if S and bool((ops.sparse_class(nm, c3[:, 2]) & (nm > c3[:, 2])).any()):
         bm8 = torch.empty(max(plan.n_bmin8, 1), dtype=torch.int16, device=dev)
     cube, _, _ = ops.triplet_cost_argmin(pts, cam_offs, F_dev, plan, bmin8=bm8)
     mark("cube")
@@ -502,17 +526,16 @@ def _device_chain(pts, cam_offs, cam_offs_host, F_dev, proj_dev, S, threshold, c
     match, cost, X, count = ops.select_triangulate(cube, plan.cube_offs, cam_offs, lplan.out_offs,
                                                    row_ind, col_ind, pts, proj_dev, threshold)
     mark("select")
-    return (match, cost, X, lstat, count, lplan.out_offs_host, (cube if keep_cube else None),
-            lplan.out_offs)
+    return _Chain(match, cost, X, lstat, count, lplan.out_offs_host, cube if keep_cube else None,
+                  lplan.out_offs)
 
 
-def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
+def _split_chain(rig: _Rig, S, threshold, free, mark) -> _Chain:
     """_device_chain over the cube-free scenes and the others as two
     contiguous sub-batches (their centroids, F and P gathered on the device),
     merged back into the batch's scene order and assignment offsets."""
+    pts, co, c3 = rig.pts, rig.cam_offs_host, rig.counts
     dev = pts.device
-    co = np.asarray(cam_offs_host, np.int64)
-    c3 = np.diff(co).reshape(S, 3)
     caps = np.minimum(c3[:, 0] * c3[:, 1], c3[:, 2])
     out_offs = np.zeros(S + 1, np.int64)
     np.cumsum(caps, out=out_offs[1:])
@@ -522,7 +545,7 @@ def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
     X = torch.zeros((max(cap, 1), 3), dtype=torch.float64, device=dev)
     status = torch.zeros(S, dtype=torch.int32, device=dev)
     count = torch.zeros(S, dtype=torch.int32, device=dev)
-    F3 = F_dev.reshape(S, 27)
+    F3 = rig.F.reshape(S, 27)
     for part in (np.nonzero(free)[0], np.nonzero(~free)[0]):
         if part.size == 0:
             continue
@@ -534,19 +557,18 @@ def _split_chain(pts, cam_offs_host, F_dev, proj_dev, S, threshold, free, mark):
              np.concatenate([np.arange(out_offs[s], out_offs[s] + caps[s]) for s in part]).astype(np.int64),
              np.arange(int(caps[part].sum()), dtype=np.int64), sub_co], dev)
         sub_pts = pts.index_select(0, sel) if rows.size else pts[:0]
-        m, c, x, st, n = _device_chain(sub_pts, sub_co_dev, sub_co,
-                                       F3.index_select(0, idx).reshape(-1),
-                                       proj_dev.index_select(0, idx), part.size, threshold,
-                                       bool(free[part[0]]), False, mark)[:5]
+        sub = _device_chain(_Rig(sub_pts, sub_co_dev, sub_co, c3[part],
+                                 F3.index_select(0, idx).reshape(-1), rig.proj.index_select(0, idx)),
+                            part.size, threshold, bool(free[part[0]]), False, mark)
         if src_rows.numel():
-            match.index_copy_(0, dst_rows, m.index_select(0, src_rows))
-            cost.index_copy_(0, dst_rows, c.index_select(0, src_rows))
-            X.index_copy_(0, dst_rows, x.index_select(0, src_rows))
-        status.index_copy_(0, idx, st)
-        count.index_copy_(0, idx, n)
+            match.index_copy_(0, dst_rows, sub.match.index_select(0, src_rows))
+            cost.index_copy_(0, dst_rows, sub.cost.index_select(0, src_rows))
+            X.index_copy_(0, dst_rows, sub.X.index_select(0, src_rows))
+        status.index_copy_(0, idx, sub.status)
+        count.index_copy_(0, idx, sub.count)
     # the merged layout's offsets, for MatchBatch.table: uploaded once
     out_offs_dev, = ops._h2d_int64([out_offs], dev)
-    return match[:cap], cost[:cap], X[:cap], status, count, out_offs, None, out_offs_dev
+    return _Chain(match[:cap], cost[:cap], X[:cap], status, count, out_offs, None, out_offs_dev)
 
 
 def _rig_inputs(batch: Sequence, n_cams: int = 3):
@@ -614,9 +636,8 @@ def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3, r
     """
     if "F" in kwargs or "proj" in kwargs:
         raise TypeError("match_capture_stream computes F and proj itself")
-    if rig not in ("host", "device", "auto"):
-        raise ValueError(f"rig: expected 'host', 'device' or 'auto', got {rig!r}")
-    if rig != "host" or int(kwargs.get("n_cams", 3)) != 3:
+    _check_rig(rig)
+    if rig != "host" or _check_n_cams(kwargs.get("n_cams", 3)) != 3:
         for cur in batches:
             yield match_captures(*cur, rig=rig, **kwargs)
         return

@@ -9,6 +9,10 @@ Ops (all ``*_out`` ops write caller-allocated tensors, like the C ABI):
   mvmatch::pairwise_residual_f64_out      e_ab kept in float64 (uniform layout)
   mvmatch::triplet_cost_argmin_out        3-camera cube + per-(i,j) argmin
 
+An op states what it accepts as one row per tensor argument, ``(tensor, name,
+dtype, numel, mode)``, checked by ``_check_args``: the mode (``EXACT``,
+``AT_LEAST``, ``ANY``) says how the element count is compared with ``numel``.
+
 Plans (``PairwisePlan`` / ``TripletPlan``) hold the host-side offset tables
 (prefix sums of the per-view detection counts) and their device copies; a
 plan is reusable for every batch with the same counts.
@@ -39,6 +43,9 @@ __all__ = [
     "cube_free_scenes", "sparse_class_bounds", "lsap_sparse_stats", "compact_matches",
     "rig_matrices", "extend_costs", "extend_select_triangulate", "compact_matches_views",
 ]
+
+f32, f64, i16, i32, i64, u8 = (torch.float32, torch.float64, torch.int16, torch.int32, torch.int64,
+                               torch.uint8)
 
 
 def _h2d_int64(arrays: List[np.ndarray], device: torch.device) -> List[Tensor]:
@@ -84,6 +91,26 @@ def _stream(t: Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def _call(fn: str, *args) -> None:
+    """The C entry point ``fn``; a status other than MVM_OK raises MvmError."""
+    _native.check(fn, getattr(_native.load(), fn)(*args))
+
+
+def _pair_arrays(pair_a: List[int], pair_b: List[int]):
+    """The camera pair lists as the int32 arrays the C ABI reads."""
+    n = len(pair_a)
+    if len(pair_b) != n:
+        raise ValueError("pair_a / pair_b differ in length")
+    return (ctypes.c_int32 * n)(*pair_a), (ctypes.c_int32 * n)(*pair_b)
+
+
+def _gpu(t: Tensor, name: str, what: str = "matcher") -> torch.device:
+    """The device of the op's leading tensor, which must be a GPU."""
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must be a GPU tensor (the {what} has no CPU path)")
+    return t.device
+
+
 def _require(t: Tensor, name: str, dtype: torch.dtype, device: torch.device) -> None:
     if t.dtype != dtype:
         raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
@@ -93,125 +120,109 @@ def _require(t: Tensor, name: str, dtype: torch.dtype, device: torch.device) -> 
         raise ValueError(f"{name}: must be contiguous")
 
 
-def _check_inputs(pts: Tensor, cam_offs: Tensor, F: Tensor, n_views: int, n_mats: int) -> None:
-    if pts.device.type != "cuda":
-        raise ValueError("pts must be a GPU tensor (the matcher has no CPU path)")
-    dev = pts.device
-    _require(pts, "pts", torch.float64, dev)
-    _require(cam_offs, "cam_offs", torch.int64, dev)
-    _require(F, "F", torch.float64, dev)
+# how _check_args compares a tensor's element count with its row's ``numel``
+EXACT, AT_LEAST, ANY = "exact", "at least", "any"
+
+
+def _check_args(dev: torch.device, rows) -> None:
+    """An op's tensor arguments against their spec, one row each: (tensor,
+    name, dtype, numel, mode).  Every tensor has the dtype, lives on ``dev``
+    and is contiguous (``_require``); it holds ``numel`` elements (EXACT), at
+    least as many (AT_LEAST), or any number (ANY: ``numel`` is not read)."""
+    for t, name, dtype, numel, mode in rows:
+        _require(t, name, dtype, dev)
+        if mode == EXACT:
+            if t.numel() != numel:
+                raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+        elif mode == AT_LEAST:
+            if t.numel() < numel:
+                raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
+        elif mode != ANY:
+            raise ValueError(f"{name}: unknown mode {mode!r}")
+
+
+def _scene_rows(pts: Tensor, cam_offs: Tensor, F: Tensor, n_views: int, n_mats: int):
+    """-> (device, rows of the three inputs the residual ops start with)."""
+    dev = _gpu(pts, "pts")
     if pts.dim() != 2 or pts.shape[1] != 2:
         raise ValueError(f"pts: expected [n, 2], got {tuple(pts.shape)}")
-    if cam_offs.numel() != n_views + 1:
-        raise ValueError(f"cam_offs: expected {n_views + 1} entries, got {cam_offs.numel()}")
-    if F.numel() != n_mats * 9:
-        raise ValueError(f"F: expected {n_mats} 3x3 matrices, got {F.numel()} values")
+    return dev, [(pts, "pts", f64, None, ANY), (cam_offs, "cam_offs", i64, n_views + 1, EXACT),
+                 (F, "F", f64, 9 * n_mats, EXACT)]
+
+
+def _gpu_op(name: str, mutates_args):
+    """``torch.library.custom_op("mvmatch::<name>")`` for an op that returns
+    None, so one fake serves every op (nothing to allocate or shape)."""
+    def wrap(fn):
+        op = torch.library.custom_op(f"mvmatch::{name}", mutates_args=mutates_args)(fn)
+        op.register_fake(lambda *args, **kwargs: None)
+        return op
+    return wrap
 
 
 # ------------------------------------------------------------------ ops ----
-@torch.library.custom_op("mvmatch::pairwise_residual_argmin_out",
-                         mutates_args=("dist", "argmin", "minval"))
+@_gpu_op("pairwise_residual_argmin_out", ("dist", "argmin", "minval"))
 def pairwise_residual_argmin_out(pts: Tensor, cam_offs: Tensor, F: Tensor, pair_a: List[int],
                                  pair_b: List[int], n_scenes: int, n_cams: int, max_n: int,
                                  dist_offs: Tensor, row_offs: Tensor, dist: Tensor,
                                  argmin: Tensor, minval: Tensor,
                                  opts: Optional[List[int]] = None, row_align: int = 1) -> None:
     n_pairs = len(pair_a)
-    _check_inputs(pts, cam_offs, F, n_scenes * n_cams, n_scenes * n_pairs)
-    for t, n, dt in ((dist_offs, "dist_offs", torch.int64), (row_offs, "row_offs", torch.int64),
-                     (dist, "dist", torch.float32), (argmin, "argmin", torch.int32),
-                     (minval, "minval", torch.float32)):
-        _require(t, n, dt, pts.device)
-    pa = (ctypes.c_int32 * n_pairs)(*pair_a)
-    pb = (ctypes.c_int32 * n_pairs)(*pair_b)
-    st = _native.load().mvm_pairwise_residual_argmin_pitched(
-        _p(pts), _p(cam_offs), _p(F), pa, pb, n_scenes, n_cams, n_pairs, max_n, row_align,
-        _p(dist_offs), _p(row_offs), _p(dist), _p(argmin), _p(minval), _opts_ref(opts),
-        _stream(pts))
-    _native.check("mvm_pairwise_residual_argmin_pitched", st)
+    dev, rows = _scene_rows(pts, cam_offs, F, n_scenes * n_cams, n_scenes * n_pairs)
+    _check_args(dev, rows + [(dist_offs, "dist_offs", i64, None, ANY), (row_offs, "row_offs", i64, None, ANY),
+                             (dist, "dist", f32, None, ANY), (argmin, "argmin", i32, None, ANY),
+                             (minval, "minval", f32, None, ANY)])
+    pa, pb = _pair_arrays(pair_a, pair_b)
+    _call("mvm_pairwise_residual_argmin_pitched", _p(pts), _p(cam_offs), _p(F), pa, pb, n_scenes,
+          n_cams, n_pairs, max_n, row_align, _p(dist_offs), _p(row_offs), _p(dist), _p(argmin),
+          _p(minval), _opts_ref(opts), _stream(pts))
 
 
-@pairwise_residual_argmin_out.register_fake
-def _(pts, cam_offs, F, pair_a, pair_b, n_scenes, n_cams, max_n, dist_offs, row_offs, dist,
-      argmin, minval, opts=None, row_align=1):
-    return None
-
-
-@torch.library.custom_op("mvmatch::pairwise_residual_f64_out", mutates_args=("e",))
+@_gpu_op("pairwise_residual_f64_out", ("e",))
 def pairwise_residual_f64_out(pts: Tensor, cam_offs: Tensor, F: Tensor, pair_a: List[int],
                               pair_b: List[int], n_scenes: int, n_cams: int, max_n: int,
                               mat_stride: int, ld: int, e: Tensor) -> None:
     n_pairs = len(pair_a)
-    _check_inputs(pts, cam_offs, F, n_scenes * n_cams, n_scenes * n_pairs)
-    _require(e, "e", torch.float64, pts.device)
-    if e.numel() < n_scenes * n_pairs * mat_stride:
-        raise ValueError("e: too small for n_scenes * n_pairs * mat_stride")
-    pa = (ctypes.c_int32 * n_pairs)(*pair_a)
-    pb = (ctypes.c_int32 * n_pairs)(*pair_b)
-    st = _native.load().mvm_pairwise_residual_f64(
-        _p(pts), _p(cam_offs), _p(F), pa, pb, n_scenes, n_cams, n_pairs, max_n, mat_stride,
-        ld, _p(e), _stream(pts))
-    _native.check("mvm_pairwise_residual_f64", st)
+    dev, rows = _scene_rows(pts, cam_offs, F, n_scenes * n_cams, n_scenes * n_pairs)
+    _check_args(dev, rows + [(e, "e", f64, n_scenes * n_pairs * mat_stride, AT_LEAST)])
+    pa, pb = _pair_arrays(pair_a, pair_b)
+    _call("mvm_pairwise_residual_f64", _p(pts), _p(cam_offs), _p(F), pa, pb, n_scenes, n_cams,
+          n_pairs, max_n, mat_stride, ld, _p(e), _stream(pts))
 
 
-@pairwise_residual_f64_out.register_fake
-def _(pts, cam_offs, F, pair_a, pair_b, n_scenes, n_cams, max_n, mat_stride, ld, e):
-    return None
-
-
-@torch.library.custom_op("mvmatch::triplet_cost_argmin_out",
-                         mutates_args=("cube", "argmin", "minval", "workspace"))
+@_gpu_op("triplet_cost_argmin_out", ("cube", "argmin", "minval", "workspace"))
 def triplet_cost_argmin_out(pts: Tensor, cam_offs: Tensor, F: Tensor, n_scenes: int, max_n: int,
                             cube_offs: Tensor, row_offs: Tensor, cube: Tensor, argmin: Tensor,
                             minval: Tensor, workspace: Tensor,
                             opts: Optional[List[int]] = None) -> None:
-    _check_inputs(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
-    for t, n, dt in ((cube_offs, "cube_offs", torch.int64), (row_offs, "row_offs", torch.int64),
-                     (cube, "cube", torch.float32), (argmin, "argmin", torch.int32),
-                     (minval, "minval", torch.float32), (workspace, "workspace", torch.uint8)):
-        _require(t, n, dt, pts.device)
-    ws_bytes = workspace.numel()
-    st = _native.load().mvm_triplet_cost_argmin_ex(
-        _p(pts), _p(cam_offs), _p(F), n_scenes, max_n, _p(cube_offs), _p(row_offs), _p(cube),
-        _p(argmin), _p(minval), _p(workspace), ws_bytes, _opts_ref(opts), _stream(pts))
-    _native.check("mvm_triplet_cost_argmin_ex", st)
+    dev, rows = _scene_rows(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
+    _check_args(dev, rows + [(cube_offs, "cube_offs", i64, None, ANY), (row_offs, "row_offs", i64, None, ANY),
+                             (cube, "cube", f32, None, ANY), (argmin, "argmin", i32, None, ANY),
+                             (minval, "minval", f32, None, ANY), (workspace, "workspace", u8, None, ANY)])
+    _call("mvm_triplet_cost_argmin_ex", _p(pts), _p(cam_offs), _p(F), n_scenes, max_n, _p(cube_offs),
+          _p(row_offs), _p(cube), _p(argmin), _p(minval), _p(workspace), workspace.numel(),
+          _opts_ref(opts), _stream(pts))
 
 
-@triplet_cost_argmin_out.register_fake
-def _(pts, cam_offs, F, n_scenes, max_n, cube_offs, row_offs, cube, argmin, minval, workspace,
-      opts=None):
-    return None
-
-
-@torch.library.custom_op("mvmatch::triplet_cost_bmin8_out",
-                         mutates_args=("cube", "argmin", "minval", "bmin8", "workspace"))
+@_gpu_op("triplet_cost_bmin8_out", ("cube", "argmin", "minval", "bmin8", "workspace"))
 def triplet_cost_bmin8_out(pts: Tensor, cam_offs: Tensor, F: Tensor, n_scenes: int, max_n: int,
                            cube_offs: Tensor, row_offs: Tensor, cube: Tensor, argmin: Tensor,
                            minval: Tensor, bmin8: Tensor, bmin8_offs: Tensor, workspace: Tensor,
                            opts: Optional[List[int]] = None) -> None:
     """triplet_cost_argmin_out + the 8-row minima the assignment reduces
     (mvm_triplet_cost_argmin_bmin8)."""
-    _check_inputs(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
-    for t, n, dt in ((cube_offs, "cube_offs", torch.int64), (row_offs, "row_offs", torch.int64),
-                     (cube, "cube", torch.float32), (argmin, "argmin", torch.int32),
-                     (minval, "minval", torch.float32), (bmin8, "bmin8", torch.int16),
-                     (bmin8_offs, "bmin8_offs", torch.int64), (workspace, "workspace", torch.uint8)):
-        _require(t, n, dt, pts.device)
-    st = _native.load().mvm_triplet_cost_argmin_bmin8(
-        _p(pts), _p(cam_offs), _p(F), n_scenes, max_n, _p(cube_offs), _p(row_offs), _p(cube),
-        _p(argmin), _p(minval), _p(bmin8), _p(bmin8_offs), _p(workspace), workspace.numel(),
-        _opts_ref(opts), _stream(pts))
-    _native.check("mvm_triplet_cost_argmin_bmin8", st)
+    dev, rows = _scene_rows(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
+    _check_args(dev, rows + [(cube_offs, "cube_offs", i64, None, ANY), (row_offs, "row_offs", i64, None, ANY),
+                             (cube, "cube", f32, None, ANY), (argmin, "argmin", i32, None, ANY),
+                             (minval, "minval", f32, None, ANY), (bmin8, "bmin8", i16, None, ANY),
+                             (bmin8_offs, "bmin8_offs", i64, None, ANY),
+                             (workspace, "workspace", u8, None, ANY)])
+    _call("mvm_triplet_cost_argmin_bmin8", _p(pts), _p(cam_offs), _p(F), n_scenes, max_n,
+          _p(cube_offs), _p(row_offs), _p(cube), _p(argmin), _p(minval), _p(bmin8), _p(bmin8_offs),
+          _p(workspace), workspace.numel(), _opts_ref(opts), _stream(pts))
 
 
-@triplet_cost_bmin8_out.register_fake
-def _(pts, cam_offs, F, n_scenes, max_n, cube_offs, row_offs, cube, argmin, minval, bmin8, bmin8_offs,
-      workspace, opts=None):
-    return None
-
-
-@torch.library.custom_op("mvmatch::lsap_solve_bmin8_out",
-                         mutates_args=("workspace", "row_ind", "col_ind", "status"))
+@_gpu_op("lsap_solve_bmin8_out", ("workspace", "row_ind", "col_ind", "status"))
 def lsap_solve_bmin8_out(cost: Tensor, cost_offs: Tensor, dims: Tensor, ws_offs: Tensor,
                          out_offs: Tensor, workspace: Tensor, row_ind: Tensor, col_ind: Tensor,
                          status: Tensor, bmin8: Tensor, bmin8_offs: Tensor, segs: Tensor,
@@ -221,84 +232,54 @@ def lsap_solve_bmin8_out(cost: Tensor, cost_offs: Tensor, dims: Tensor, ws_offs:
     dev = cost.device
     if dev.type != "cuda" or cost.dtype != torch.float32:
         raise ValueError("cost must be a float32 GPU tensor")
-    for t, n, dt in ((cost_offs, "cost_offs", torch.int64), (dims, "dims", torch.int64),
-                     (ws_offs, "ws_offs", torch.int64), (out_offs, "out_offs", torch.int64),
-                     (workspace, "workspace", torch.uint8), (row_ind, "row_ind", torch.int64),
-                     (col_ind, "col_ind", torch.int64), (status, "status", torch.int32),
-                     (bmin8, "bmin8", torch.int16), (bmin8_offs, "bmin8_offs", torch.int64),
-                     (segs, "segs", torch.int64)):
-        _require(t, n, dt, dev)
-    st = _native.load().mvm_lsap_solve_ex3(_p(cost), _native.MVM_F32, _p(cost_offs), _p(dims),
-                                           status.numel(), _p(ws_offs), _p(out_offs), _p(workspace),
-                                           workspace.numel(), _p(row_ind), _p(col_ind), _p(status),
-                                           long_min, long_max, short_max, _p(bmin8), _p(bmin8_offs),
-                                           _p(segs), _opts_ref(opts), _stream(cost))
-    _native.check("mvm_lsap_solve_ex3", st)
+    _check_args(dev, [(cost_offs, "cost_offs", i64, None, ANY), (dims, "dims", i64, None, ANY),
+                      (ws_offs, "ws_offs", i64, None, ANY), (out_offs, "out_offs", i64, None, ANY),
+                      (workspace, "workspace", u8, None, ANY), (row_ind, "row_ind", i64, None, ANY),
+                      (col_ind, "col_ind", i64, None, ANY), (status, "status", i32, None, ANY),
+                      (bmin8, "bmin8", i16, None, ANY), (bmin8_offs, "bmin8_offs", i64, None, ANY),
+                      (segs, "segs", i64, None, ANY)])
+    _call("mvm_lsap_solve_ex3", _p(cost), _native.MVM_F32, _p(cost_offs), _p(dims), status.numel(),
+          _p(ws_offs), _p(out_offs), _p(workspace), workspace.numel(), _p(row_ind), _p(col_ind),
+          _p(status), long_min, long_max, short_max, _p(bmin8), _p(bmin8_offs), _p(segs),
+          _opts_ref(opts), _stream(cost))
 
 
-@lsap_solve_bmin8_out.register_fake
-def _(cost, cost_offs, dims, ws_offs, out_offs, workspace, row_ind, col_ind, status, bmin8, bmin8_offs,
-      segs, long_min, long_max, short_max, opts=None):
-    return None
-
-
-@torch.library.custom_op("mvmatch::lsap_solve_out",
-                         mutates_args=("workspace", "row_ind", "col_ind", "status"))
+@_gpu_op("lsap_solve_out", ("workspace", "row_ind", "col_ind", "status"))
 def lsap_solve_out(cost: Tensor, cost_offs: Tensor, dims: Tensor, ws_offs: Tensor,
                    out_offs: Tensor, workspace: Tensor, row_ind: Tensor, col_ind: Tensor,
                    status: Tensor, long_min: int = 1, long_max: int = 2 ** 62,
                    opts: Optional[List[int]] = None, short_max: int = -1) -> None:
-    dev = cost.device
-    if dev.type != "cuda":
-        raise ValueError("cost must be a GPU tensor (the matcher has no CPU path)")
+    dev = _gpu(cost, "cost")
     if cost.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"cost: expected float32 or float64, got {cost.dtype}")
-    for t, n, dt in ((cost, "cost", cost.dtype), (cost_offs, "cost_offs", torch.int64),
-                     (dims, "dims", torch.int64), (ws_offs, "ws_offs", torch.int64),
-                     (out_offs, "out_offs", torch.int64), (workspace, "workspace", torch.uint8),
-                     (row_ind, "row_ind", torch.int64), (col_ind, "col_ind", torch.int64),
-                     (status, "status", torch.int32)):
-        _require(t, n, dt, dev)
-    n = status.numel()
+    _check_args(dev, [(cost, "cost", cost.dtype, None, ANY), (cost_offs, "cost_offs", i64, None, ANY),
+                      (dims, "dims", i64, None, ANY), (ws_offs, "ws_offs", i64, None, ANY),
+                      (out_offs, "out_offs", i64, None, ANY), (workspace, "workspace", u8, None, ANY),
+                      (row_ind, "row_ind", i64, None, ANY), (col_ind, "col_ind", i64, None, ANY),
+                      (status, "status", i32, None, ANY)])
     dtype = _native.MVM_F64 if cost.dtype == torch.float64 else _native.MVM_F32
-    st = _native.load().mvm_lsap_solve_ex2(_p(cost), dtype, _p(cost_offs), _p(dims), n, _p(ws_offs),
-                                           _p(out_offs), _p(workspace), workspace.numel(),
-                                           _p(row_ind), _p(col_ind), _p(status), long_min,
-                                           long_max, long_max if short_max < 0 else short_max,
-                                           _opts_ref(opts), _stream(cost))
-    _native.check("mvm_lsap_solve_ex2", st)
+    _call("mvm_lsap_solve_ex2", _p(cost), dtype, _p(cost_offs), _p(dims), status.numel(), _p(ws_offs),
+          _p(out_offs), _p(workspace), workspace.numel(), _p(row_ind), _p(col_ind), _p(status),
+          long_min, long_max, long_max if short_max < 0 else short_max, _opts_ref(opts),
+          _stream(cost))
 
 
-@lsap_solve_out.register_fake
-def _(cost, cost_offs, dims, ws_offs, out_offs, workspace, row_ind, col_ind, status, long_min=1,
-      long_max=2 ** 62, opts=None, short_max=-1):
-    return None
-
-
-@torch.library.custom_op("mvmatch::triplet_minima_out", mutates_args=("bmin8", "resid"))
+@_gpu_op("triplet_minima_out", ("bmin8", "resid"))
 def triplet_minima_out(pts: Tensor, cam_offs: Tensor, F: Tensor, n_scenes: int, max_n: int,
                        bmin8: Tensor, bmin8_offs: Tensor, bm32: Tensor, bm32_offs: Tensor,
                        resid: Tensor, opts: Optional[List[int]] = None) -> None:
     """The cube's 8-row minima, the assignment's 32-column block minima and
     every scene's fp64 pair residuals, no cube (mvm_triplet_minima, ABI 7)."""
-    _check_inputs(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
-    for t, n, dt in ((bmin8, "bmin8", torch.int16), (bmin8_offs, "bmin8_offs", torch.int64),
-                     (bm32, "bm32", torch.int16), (bm32_offs, "bm32_offs", torch.int64),
-                     (resid, "resid", torch.uint8)):
-        _require(t, n, dt, pts.device)
-    st = _native.load().mvm_triplet_minima(_p(pts), _p(cam_offs), _p(F), n_scenes, max_n, _p(bmin8),
-                                           _p(bmin8_offs), _p(bm32), _p(bm32_offs), _p(resid),
-                                           resid.numel(), _opts_ref(opts), _stream(pts))
-    _native.check("mvm_triplet_minima", st)
+    dev, rows = _scene_rows(pts, cam_offs, F, n_scenes * 3, n_scenes * 3)
+    _check_args(dev, rows + [(bmin8, "bmin8", i16, None, ANY), (bmin8_offs, "bmin8_offs", i64, None, ANY),
+                             (bm32, "bm32", i16, None, ANY), (bm32_offs, "bm32_offs", i64, None, ANY),
+                             (resid, "resid", u8, None, ANY)])
+    _call("mvm_triplet_minima", _p(pts), _p(cam_offs), _p(F), n_scenes, max_n, _p(bmin8),
+          _p(bmin8_offs), _p(bm32), _p(bm32_offs), _p(resid), resid.numel(), _opts_ref(opts),
+          _stream(pts))
 
 
-@triplet_minima_out.register_fake
-def _(pts, cam_offs, F, n_scenes, max_n, bmin8, bmin8_offs, bm32, bm32_offs, resid, opts=None):
-    return None
-
-
-@torch.library.custom_op("mvmatch::lsap_solve_resid_out",
-                         mutates_args=("workspace", "row_ind", "col_ind", "status"))
+@_gpu_op("lsap_solve_resid_out", ("workspace", "row_ind", "col_ind", "status"))
 def lsap_solve_resid_out(dims: Tensor, ws_offs: Tensor, out_offs: Tensor, workspace: Tensor,
                          row_ind: Tensor, col_ind: Tensor, status: Tensor, bmin8: Tensor,
                          bmin8_offs: Tensor, bm32: Tensor, bm32_offs: Tensor, segs: Tensor,
@@ -306,225 +287,134 @@ def lsap_solve_resid_out(dims: Tensor, ws_offs: Tensor, out_offs: Tensor, worksp
                          opts: Optional[List[int]] = None) -> None:
     """The assignment of every flattened cube of a triplet_minima batch, from
     its 8-row minima and pair residuals (mvm_lsap_solve_resid, ABI 7)."""
-    dev = dims.device
-    if dev.type != "cuda":
-        raise ValueError("dims must be a GPU tensor (the matcher has no CPU path)")
-    for t, n, dt in ((dims, "dims", torch.int64), (ws_offs, "ws_offs", torch.int64),
-                     (out_offs, "out_offs", torch.int64), (workspace, "workspace", torch.uint8),
-                     (row_ind, "row_ind", torch.int64), (col_ind, "col_ind", torch.int64),
-                     (status, "status", torch.int32), (bmin8, "bmin8", torch.int16),
-                     (bmin8_offs, "bmin8_offs", torch.int64), (bm32, "bm32", torch.int16),
-                     (bm32_offs, "bm32_offs", torch.int64), (segs, "segs", torch.int64),
-                     (resid, "resid", torch.uint8)):
-        _require(t, n, dt, dev)
-    st = _native.load().mvm_lsap_solve_resid(_p(dims), status.numel(), _p(ws_offs), _p(out_offs),
-                                             _p(workspace), workspace.numel(), _p(row_ind), _p(col_ind),
-                                             _p(status), long_min, long_max, short_max, _p(bmin8),
-                                             _p(bmin8_offs), _p(bm32), _p(bm32_offs), _p(segs), _p(resid),
-                                             max_n, _opts_ref(opts), _stream(dims))
-    _native.check("mvm_lsap_solve_resid", st)
+    dev = _gpu(dims, "dims")
+    _check_args(dev, [(dims, "dims", i64, None, ANY), (ws_offs, "ws_offs", i64, None, ANY),
+                      (out_offs, "out_offs", i64, None, ANY), (workspace, "workspace", u8, None, ANY),
+                      (row_ind, "row_ind", i64, None, ANY), (col_ind, "col_ind", i64, None, ANY),
+                      (status, "status", i32, None, ANY), (bmin8, "bmin8", i16, None, ANY),
+                      (bmin8_offs, "bmin8_offs", i64, None, ANY), (bm32, "bm32", i16, None, ANY),
+                      (bm32_offs, "bm32_offs", i64, None, ANY), (segs, "segs", i64, None, ANY),
+                      (resid, "resid", u8, None, ANY)])
+    _call("mvm_lsap_solve_resid", _p(dims), status.numel(), _p(ws_offs), _p(out_offs), _p(workspace),
+          workspace.numel(), _p(row_ind), _p(col_ind), _p(status), long_min, long_max, short_max,
+          _p(bmin8), _p(bmin8_offs), _p(bm32), _p(bm32_offs), _p(segs), _p(resid), max_n,
+          _opts_ref(opts), _stream(dims))
 
 
-@lsap_solve_resid_out.register_fake
-def _(dims, ws_offs, out_offs, workspace, row_ind, col_ind, status, bmin8, bmin8_offs, bm32, bm32_offs,
-      segs, resid, max_n, long_min, long_max, short_max, opts=None):
-    return None
-
-
-@torch.library.custom_op("mvmatch::pack_detections_out",
-                         mutates_args=("counts", "cam_offs", "pts", "boxes_out", "status"))
+@_gpu_op("pack_detections_out", ("counts", "cam_offs", "pts", "boxes_out", "status"))
 def pack_detections_out(boxes: Tensor, conf: Tensor, cls: Tensor, img_offs: Tensor,
                         conf_thresh: float, class_id: float, counts: Tensor, cam_offs: Tensor,
                         pts: Tensor, boxes_out: Tensor, status: Tensor) -> None:
-    dev = boxes.device
-    if dev.type != "cuda":
-        raise ValueError("boxes must be a GPU tensor (the packer has no CPU path)")
-    n_img = counts.numel()
-    n = boxes.shape[0] if boxes.dim() == 2 else -1
+    dev = _gpu(boxes, "boxes", "packer")
     if boxes.dim() != 2 or boxes.shape[1] != 4:
         raise ValueError("boxes must be [n, 4] (xyxy)")
-    for t, name, dt, numel in ((boxes, "boxes", torch.float32, 4 * n), (conf, "conf", torch.float32, n),
-                               (cls, "cls", torch.float32, n), (img_offs, "img_offs", torch.int64, n_img + 1),
-                               (counts, "counts", torch.int32, n_img),
-                               (cam_offs, "cam_offs", torch.int64, n_img + 1),
-                               (pts, "pts", torch.float64, 2 * n),
-                               (boxes_out, "boxes_out", torch.int32, 4 * n), (status, "status", torch.int32, 1)):
-        _require(t, name, dt, dev)
-        if t.numel() < numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
-    st = _native.load().mvm_pack_detections(_p(boxes), _p(conf), _p(cls), _p(img_offs), n_img,
-                                            float(conf_thresh), float(class_id), _p(counts),
-                                            _p(cam_offs), _p(pts), _p(boxes_out), _p(status),
-                                            _stream(boxes))
-    _native.check("mvm_pack_detections", st)
+    n, n_img = boxes.shape[0], counts.numel()
+    _check_args(dev, [(boxes, "boxes", f32, 4 * n, AT_LEAST), (conf, "conf", f32, n, AT_LEAST),
+                      (cls, "cls", f32, n, AT_LEAST), (img_offs, "img_offs", i64, n_img + 1, AT_LEAST),
+                      (counts, "counts", i32, n_img, AT_LEAST),
+                      (cam_offs, "cam_offs", i64, n_img + 1, AT_LEAST), (pts, "pts", f64, 2 * n, AT_LEAST),
+                      (boxes_out, "boxes_out", i32, 4 * n, AT_LEAST), (status, "status", i32, 1, AT_LEAST)])
+    _call("mvm_pack_detections", _p(boxes), _p(conf), _p(cls), _p(img_offs), n_img, float(conf_thresh),
+          float(class_id), _p(counts), _p(cam_offs), _p(pts), _p(boxes_out), _p(status),
+          _stream(boxes))
 
 
-@pack_detections_out.register_fake
-def _(boxes, conf, cls, img_offs, conf_thresh, class_id, counts, cam_offs, pts, boxes_out, status):
-    return None
-
-
-@torch.library.custom_op("mvmatch::triangulate_dlt_out", mutates_args=("X",))
+@_gpu_op("triangulate_dlt_out", ("X",))
 def triangulate_dlt_out(proj: Tensor, set_of_point: Optional[Tensor], pts2d: Tensor,
                         X: Tensor) -> None:
-    dev = pts2d.device
-    if dev.type != "cuda":
-        raise ValueError("pts2d must be a GPU tensor (the triangulator has no CPU path)")
+    dev = _gpu(pts2d, "pts2d", "triangulator")
     if pts2d.dim() != 3 or pts2d.shape[2] != 2:
         raise ValueError("pts2d must be [n_points, n_views, 2]")
     n_points, n_views = int(pts2d.shape[0]), int(pts2d.shape[1])
-    _require(pts2d, "pts2d", torch.float64, dev)
-    _require(proj, "proj", torch.float64, dev)
-    _require(X, "X", torch.float64, dev)
+    rows = [(pts2d, "pts2d", f64, None, ANY), (proj, "proj", f64, None, ANY),
+            (X, "X", f64, 3 * n_points, AT_LEAST)]
+    if set_of_point is not None:
+        rows.append((set_of_point, "set_of_point", i32, n_points, EXACT))
+    _check_args(dev, rows)
     if proj.dim() != 4 or tuple(proj.shape[1:]) != (n_views, 3, 4):
         raise ValueError("proj must be [n_sets, n_views, 3, 4]")
-    if X.numel() < 3 * n_points:
-        raise ValueError("X must hold [n_points, 3]")
-    if set_of_point is None:
-        if proj.shape[0] < n_points:
-            raise ValueError("without set_of_point, proj needs one set per point")
-    else:
-        _require(set_of_point, "set_of_point", torch.int32, dev)
-        if set_of_point.numel() != n_points:
-            raise ValueError("set_of_point must have n_points entries")
-    st = _native.load().mvm_triangulate_dlt(_p(proj), _p(set_of_point), _p(pts2d), n_points,
-                                            n_views, _p(X), _stream(pts2d))
-    _native.check("mvm_triangulate_dlt", st)
+    if set_of_point is None and proj.shape[0] < n_points:
+        raise ValueError("without set_of_point, proj needs one set per point")
+    _call("mvm_triangulate_dlt", _p(proj), _p(set_of_point), _p(pts2d), n_points, n_views, _p(X),
+          _stream(pts2d))
 
 
-@triangulate_dlt_out.register_fake
-def _(proj, set_of_point, pts2d, X):
-    return None
-
-
-@torch.library.custom_op("mvmatch::select_triangulate_out",
-                         mutates_args=("match", "cost", "X", "count"))
+@_gpu_op("select_triangulate_out", ("match", "cost", "X", "count"))
 def select_triangulate_out(cube: Tensor, cube_offs: Tensor, cam_offs: Tensor, lsap_offs: Tensor,
                            row_ind: Tensor, col_ind: Tensor, pts: Tensor, proj: Tensor,
                            threshold: float, match: Tensor, cost: Tensor, X: Tensor,
                            count: Tensor) -> None:
-    dev = cube.device
-    if dev.type != "cuda":
-        raise ValueError("cube must be a GPU tensor (the matcher has no CPU path)")
-    n_scenes = count.numel()
-    for t, name, dt, numel in ((cube, "cube", torch.float32, 0),
-                               (cube_offs, "cube_offs", torch.int64, n_scenes + 1),
-                               (cam_offs, "cam_offs", torch.int64, 3 * n_scenes + 1),
-                               (lsap_offs, "lsap_offs", torch.int64, n_scenes + 1),
-                               (row_ind, "row_ind", torch.int64, 0), (col_ind, "col_ind", torch.int64, 0),
-                               (pts, "pts", torch.float64, 0), (proj, "proj", torch.float64, 36 * n_scenes),
-                               (match, "match", torch.int32, 3 * row_ind.numel()),
-                               (cost, "cost", torch.float32, row_ind.numel()),
-                               (X, "X", torch.float64, 3 * row_ind.numel()),
-                               (count, "count", torch.int32, 0)):
-        _require(t, name, dt, dev)
-        if numel and t.numel() != numel and name in ("cube_offs", "cam_offs", "lsap_offs", "proj"):
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
-        if numel and t.numel() < numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
-    if col_ind.numel() != row_ind.numel():
+    dev = _gpu(cube, "cube")
+    n_scenes, n_out = count.numel(), row_ind.numel()
+    _check_args(dev, [(cube, "cube", f32, None, ANY), (cube_offs, "cube_offs", i64, n_scenes + 1, EXACT),
+                      (cam_offs, "cam_offs", i64, 3 * n_scenes + 1, EXACT),
+                      (lsap_offs, "lsap_offs", i64, n_scenes + 1, EXACT),
+                      (row_ind, "row_ind", i64, None, ANY), (col_ind, "col_ind", i64, None, ANY),
+                      (pts, "pts", f64, None, ANY),
+                      (proj, "proj", f64, 36 * n_scenes, EXACT if n_scenes else ANY),   # no scene: not read
+                      (match, "match", i32, 3 * n_out, AT_LEAST), (cost, "cost", f32, n_out, AT_LEAST),
+                      (X, "X", f64, 3 * n_out, AT_LEAST), (count, "count", i32, None, ANY)])
+    if col_ind.numel() != n_out:
         raise ValueError("row_ind / col_ind differ in length")
-    st = _native.load().mvm_select_triangulate(
-        _p(cube), _p(cube_offs), _p(cam_offs), _p(lsap_offs), _p(row_ind), _p(col_ind), _p(pts),
-        _p(proj), n_scenes, float(threshold), _p(match), _p(cost), _p(X), _p(count), _stream(cube))
-    _native.check("mvm_select_triangulate", st)
+    _call("mvm_select_triangulate", _p(cube), _p(cube_offs), _p(cam_offs), _p(lsap_offs), _p(row_ind),
+          _p(col_ind), _p(pts), _p(proj), n_scenes, float(threshold), _p(match), _p(cost), _p(X),
+          _p(count), _stream(cube))
 
 
-@select_triangulate_out.register_fake
-def _(cube, cube_offs, cam_offs, lsap_offs, row_ind, col_ind, pts, proj, threshold, match, cost,
-      X, count):
-    return None
-
-
-@torch.library.custom_op("mvmatch::select_triangulate_resid_out",
-                         mutates_args=("match", "cost", "X", "count"))
+@_gpu_op("select_triangulate_resid_out", ("match", "cost", "X", "count"))
 def select_triangulate_resid_out(resid: Tensor, max_n: int, cam_offs: Tensor, lsap_offs: Tensor,
                                  row_ind: Tensor, col_ind: Tensor, pts: Tensor, proj: Tensor,
                                  threshold: float, match: Tensor, cost: Tensor, X: Tensor,
                                  count: Tensor) -> None:
     """select_triangulate_out with each assigned entry recomputed from a
     triplet_minima batch's residuals (mvm_select_triangulate_resid, ABI 7)."""
-    dev = pts.device
-    if dev.type != "cuda":
-        raise ValueError("pts must be a GPU tensor (the matcher has no CPU path)")
-    n_scenes = count.numel()
-    for t, name, dt, numel in ((resid, "resid", torch.uint8, 0),
-                               (cam_offs, "cam_offs", torch.int64, 3 * n_scenes + 1),
-                               (lsap_offs, "lsap_offs", torch.int64, n_scenes + 1),
-                               (row_ind, "row_ind", torch.int64, 0), (col_ind, "col_ind", torch.int64, 0),
-                               (pts, "pts", torch.float64, 0), (proj, "proj", torch.float64, 36 * n_scenes),
-                               (match, "match", torch.int32, 3 * row_ind.numel()),
-                               (cost, "cost", torch.float32, row_ind.numel()),
-                               (X, "X", torch.float64, 3 * row_ind.numel()),
-                               (count, "count", torch.int32, 0)):
-        _require(t, name, dt, dev)
-        if numel and t.numel() != numel and name in ("cam_offs", "lsap_offs", "proj"):
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
-        if numel and t.numel() < numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
-    if col_ind.numel() != row_ind.numel():
+    dev = _gpu(pts, "pts")
+    n_scenes, n_out = count.numel(), row_ind.numel()
+    _check_args(dev, [(resid, "resid", u8, None, ANY), (cam_offs, "cam_offs", i64, 3 * n_scenes + 1, EXACT),
+                      (lsap_offs, "lsap_offs", i64, n_scenes + 1, EXACT),
+                      (row_ind, "row_ind", i64, None, ANY), (col_ind, "col_ind", i64, None, ANY),
+                      (pts, "pts", f64, None, ANY),
+                      (proj, "proj", f64, 36 * n_scenes, EXACT if n_scenes else ANY),   # no scene: not read
+                      (match, "match", i32, 3 * n_out, AT_LEAST), (cost, "cost", f32, n_out, AT_LEAST),
+                      (X, "X", f64, 3 * n_out, AT_LEAST), (count, "count", i32, None, ANY)])
+    if col_ind.numel() != n_out:
         raise ValueError("row_ind / col_ind differ in length")
-    st = _native.load().mvm_select_triangulate_resid(
-        _p(resid), max_n, _p(cam_offs), _p(lsap_offs), _p(row_ind), _p(col_ind), _p(pts), _p(proj),
-        n_scenes, float(threshold), _p(match), _p(cost), _p(X), _p(count), _stream(pts))
-    _native.check("mvm_select_triangulate_resid", st)
+    _call("mvm_select_triangulate_resid", _p(resid), max_n, _p(cam_offs), _p(lsap_offs), _p(row_ind),
+          _p(col_ind), _p(pts), _p(proj), n_scenes, float(threshold), _p(match), _p(cost), _p(X),
+          _p(count), _stream(pts))
 
 
-@select_triangulate_resid_out.register_fake
-def _(resid, max_n, cam_offs, lsap_offs, row_ind, col_ind, pts, proj, threshold, match, cost, X, count):
-    return None
-
-
-@torch.library.custom_op("mvmatch::compact_matches_out",
-                         mutates_args=("dense_offs", "scene_out", "match_out", "cost_out", "X_out",
-                                       "boxes_out", "cent_out"))
+@_gpu_op("compact_matches_out", ("dense_offs", "scene_out", "match_out", "cost_out", "X_out", "boxes_out",
+                                 "cent_out"))
 def compact_matches_out(match: Tensor, cost: Tensor, X: Tensor, count: Tensor, seg_offs: Tensor,
                         pts: Tensor, boxes: Tensor, cam_offs: Tensor, scene_base: int,
                         dense_offs: Tensor, scene_out: Tensor, match_out: Tensor, cost_out: Tensor,
                         X_out: Tensor, boxes_out: Tensor, cent_out: Tensor) -> None:
     """The select kernels' matches as dense, self-contained rows
     (mvm_compact_matches, ABI 8).  Outputs hold ``match.shape[0]`` rows."""
-    dev = match.device
-    if dev.type != "cuda":
-        raise ValueError("match must be a GPU tensor (the table has no CPU path)")
-    n_scenes = count.numel()
-    cap = int(match.shape[0]) if match.dim() == 2 else -1
+    dev = _gpu(match, "match", "table")
     if match.dim() != 2 or match.shape[1] != 3:
         raise ValueError("match must be [cap, 3]")
-    for t, name, dt, numel in ((match, "match", torch.int32, 3 * cap), (cost, "cost", torch.float32, cap),
-                               (X, "X", torch.float64, 3 * cap), (count, "count", torch.int32, n_scenes),
-                               (seg_offs, "seg_offs", torch.int64, n_scenes + 1),
-                               (pts, "pts", torch.float64, 0), (boxes, "boxes", torch.int32, 0),
-                               (cam_offs, "cam_offs", torch.int64, 3 * n_scenes + 1),
-                               (dense_offs, "dense_offs", torch.int64, n_scenes + 1),
-                               (scene_out, "scene_out", torch.int32, cap),
-                               (match_out, "match_out", torch.int32, 3 * cap),
-                               (cost_out, "cost_out", torch.float32, cap),
-                               (X_out, "X_out", torch.float64, 3 * cap),
-                               (boxes_out, "boxes_out", torch.int32, 12 * cap),
-                               (cent_out, "cent_out", torch.float64, 6 * cap)):
-        _require(t, name, dt, dev)
-        if numel and t.numel() != numel and name in ("seg_offs", "cam_offs", "dense_offs"):
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
-        if t.numel() < numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
+    n_scenes, cap = count.numel(), int(match.shape[0])
+    _check_args(dev, [(match, "match", i32, 3 * cap, AT_LEAST), (cost, "cost", f32, cap, AT_LEAST),
+                      (X, "X", f64, 3 * cap, AT_LEAST), (count, "count", i32, n_scenes, AT_LEAST),
+                      (seg_offs, "seg_offs", i64, n_scenes + 1, EXACT),
+                      (pts, "pts", f64, None, ANY), (boxes, "boxes", i32, None, ANY),
+                      (cam_offs, "cam_offs", i64, 3 * n_scenes + 1, EXACT),
+                      (dense_offs, "dense_offs", i64, n_scenes + 1, EXACT),
+                      (scene_out, "scene_out", i32, cap, AT_LEAST),
+                      (match_out, "match_out", i32, 3 * cap, AT_LEAST),
+                      (cost_out, "cost_out", f32, cap, AT_LEAST), (X_out, "X_out", f64, 3 * cap, AT_LEAST),
+                      (boxes_out, "boxes_out", i32, 12 * cap, AT_LEAST),
+                      (cent_out, "cent_out", f64, 6 * cap, AT_LEAST)])
     if boxes.numel() != 2 * pts.numel():
         raise ValueError("pts [n, 2] and boxes [n, 4] differ in rows")
-    st = _native.load().mvm_compact_matches(
-        _p(match), _p(cost), _p(X), _p(count), _p(seg_offs), _p(pts), _p(boxes), _p(cam_offs),
-        n_scenes, int(scene_base), _p(dense_offs), _p(scene_out), _p(match_out), _p(cost_out),
-        _p(X_out), _p(boxes_out), _p(cent_out), _stream(match))
-    _native.check("mvm_compact_matches", st)
+    _call("mvm_compact_matches", _p(match), _p(cost), _p(X), _p(count), _p(seg_offs), _p(pts),
+          _p(boxes), _p(cam_offs), n_scenes, int(scene_base), _p(dense_offs), _p(scene_out),
+          _p(match_out), _p(cost_out), _p(X_out), _p(boxes_out), _p(cent_out), _stream(match))
 
 
-@compact_matches_out.register_fake
-def _(match, cost, X, count, seg_offs, pts, boxes, cam_offs, scene_base, dense_offs, scene_out,
-      match_out, cost_out, X_out, boxes_out, cent_out):
-    return None
-
-
-@torch.library.custom_op("mvmatch::compact_matches_views_out",
-                         mutates_args=("dense_offs", "scene_out", "views_out", "n_views_out", "cost_out",
+@_gpu_op("compact_matches_views_out", ("dense_offs", "scene_out", "views_out", "n_views_out", "cost_out",
                                        "ext_cost_out", "X_out", "boxes_out", "cent_out", "reproj_out"))
 def compact_matches_views_out(views: Tensor, cost: Tensor, ext_cost: Tensor, X: Tensor, count: Tensor,
                               seg_offs: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tensor,
@@ -535,135 +425,90 @@ def compact_matches_views_out(views: Tensor, cost: Tensor, ext_cost: Tensor, X: 
     """The matches of a C-camera batch as dense, self-contained rows with the
     reprojection residual of every kept view (mvm_compact_matches_views).
     ``views`` [cap, C] gives C; outputs hold ``cap`` rows."""
-    dev = views.device
-    if dev.type != "cuda":
-        raise ValueError("views must be a GPU tensor (the table has no CPU path)")
+    dev = _gpu(views, "views", "table")
     n_scenes = count.numel()
     if views.dim() != 2 or not 3 <= views.shape[1] <= _native.MVM_MAX_CAMS:
         raise ValueError(f"views must be [cap, C], 3 <= C <= {_native.MVM_MAX_CAMS}")
     cap, C = int(views.shape[0]), int(views.shape[1])
-    for t, name, dt, numel in ((views, "views", torch.int32, C * cap), (cost, "cost", torch.float32, cap),
-                               (ext_cost, "ext_cost", torch.float32, (C - 3) * cap),
-                               (X, "X", torch.float64, 3 * cap), (count, "count", torch.int32, n_scenes),
-                               (seg_offs, "seg_offs", torch.int64, n_scenes + 1),
-                               (pts, "pts", torch.float64, 0), (boxes, "boxes", torch.int32, 0),
-                               (cam_offs, "cam_offs", torch.int64, C * n_scenes + 1),
-                               (proj, "proj", torch.float64, 12 * C * n_scenes),
-                               (dense_offs, "dense_offs", torch.int64, n_scenes + 1),
-                               (scene_out, "scene_out", torch.int32, cap),
-                               (views_out, "views_out", torch.int32, C * cap),
-                               (n_views_out, "n_views_out", torch.int32, cap),
-                               (cost_out, "cost_out", torch.float32, cap),
-                               (ext_cost_out, "ext_cost_out", torch.float32, (C - 3) * cap),
-                               (X_out, "X_out", torch.float64, 3 * cap),
-                               (boxes_out, "boxes_out", torch.int32, 4 * C * cap),
-                               (cent_out, "cent_out", torch.float64, 2 * C * cap),
-                               (reproj_out, "reproj_out", torch.float64, C * cap)):
-        _require(t, name, dt, dev)
-        if numel and t.numel() != numel and name in ("seg_offs", "cam_offs", "dense_offs", "proj"):
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
-        if t.numel() < numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, needs {numel}")
+    _check_args(dev, [(views, "views", i32, C * cap, AT_LEAST), (cost, "cost", f32, cap, AT_LEAST),
+                      (ext_cost, "ext_cost", f32, (C - 3) * cap, AT_LEAST),
+                      (X, "X", f64, 3 * cap, AT_LEAST), (count, "count", i32, n_scenes, AT_LEAST),
+                      (seg_offs, "seg_offs", i64, n_scenes + 1, EXACT),
+                      (pts, "pts", f64, None, ANY), (boxes, "boxes", i32, None, ANY),
+                      (cam_offs, "cam_offs", i64, C * n_scenes + 1, EXACT),
+                      (proj, "proj", f64, 12 * C * n_scenes, EXACT if n_scenes else ANY),   # no scene: not read
+                      (dense_offs, "dense_offs", i64, n_scenes + 1, EXACT),
+                      (scene_out, "scene_out", i32, cap, AT_LEAST),
+                      (views_out, "views_out", i32, C * cap, AT_LEAST),
+                      (n_views_out, "n_views_out", i32, cap, AT_LEAST),
+                      (cost_out, "cost_out", f32, cap, AT_LEAST),
+                      (ext_cost_out, "ext_cost_out", f32, (C - 3) * cap, AT_LEAST),
+                      (X_out, "X_out", f64, 3 * cap, AT_LEAST),
+                      (boxes_out, "boxes_out", i32, 4 * C * cap, AT_LEAST),
+                      (cent_out, "cent_out", f64, 2 * C * cap, AT_LEAST),
+                      (reproj_out, "reproj_out", f64, C * cap, AT_LEAST)])
     if boxes.numel() != 2 * pts.numel():
         raise ValueError("pts [n, 2] and boxes [n, 4] differ in rows")
-    st = _native.load().mvm_compact_matches_views(
-        _p(views), _p(cost), _p(ext_cost), _p(X), _p(count), _p(seg_offs), _p(pts), _p(boxes),
-        _p(cam_offs), _p(proj), n_scenes, C, int(scene_base), _p(dense_offs), _p(scene_out),
-        _p(views_out), _p(n_views_out), _p(cost_out), _p(ext_cost_out), _p(X_out), _p(boxes_out),
-        _p(cent_out), _p(reproj_out), _stream(views))
-    _native.check("mvm_compact_matches_views", st)
+    _call("mvm_compact_matches_views", _p(views), _p(cost), _p(ext_cost), _p(X), _p(count), _p(seg_offs),
+          _p(pts), _p(boxes), _p(cam_offs), _p(proj), n_scenes, C, int(scene_base), _p(dense_offs),
+          _p(scene_out), _p(views_out), _p(n_views_out), _p(cost_out), _p(ext_cost_out), _p(X_out),
+          _p(boxes_out), _p(cent_out), _p(reproj_out), _stream(views))
 
 
-@compact_matches_views_out.register_fake
-def _(views, cost, ext_cost, X, count, seg_offs, pts, boxes, cam_offs, proj, scene_base, dense_offs,
-      scene_out, views_out, n_views_out, cost_out, ext_cost_out, X_out, boxes_out, cent_out, reproj_out):
-    return None
-
-
-@torch.library.custom_op("mvmatch::rig_matrices_out", mutates_args=("F", "proj", "status"))
+@_gpu_op("rig_matrices_out", ("F", "proj", "status"))
 def rig_matrices_out(K: Tensor, RT: Tensor, pair_a: List[int], pair_b: List[int], F: Tensor,
                      proj: Tensor, status: Tensor) -> None:
     """F of every (capture, pair) and P = K @ RT[:3] of every (capture, camera)
     on the device (mvm_rig_matrices).  ``proj`` empty: not produced."""
-    dev = K.device
-    if dev.type != "cuda":
-        raise ValueError("K must be a GPU tensor (the rig kernel has no CPU path)")
+    dev = _gpu(K, "K", "rig kernel")
     if K.dim() != 4 or tuple(K.shape[2:]) != (3, 3):
         raise ValueError(f"K: expected [S, C, 3, 3], got {tuple(K.shape)}")
     S, C = int(K.shape[0]), int(K.shape[1])
     if tuple(RT.shape) != (S, C, 4, 4):
         raise ValueError(f"RT: expected {(S, C, 4, 4)}, got {tuple(RT.shape)}")
+    pa, pb = _pair_arrays(pair_a, pair_b)
     n_pairs = len(pair_a)
-    if len(pair_b) != n_pairs:
-        raise ValueError("pair_a / pair_b differ in length")
-    for t, name, dt, numel in ((K, "K", torch.float32, 9 * S * C), (RT, "RT", torch.float64, 16 * S * C),
-                               (F, "F", torch.float64, 9 * S * n_pairs),
-                               (proj, "proj", torch.float64, 12 * S * C if proj.numel() else 0),
-                               (status, "status", torch.int32, S)):
-        _require(t, name, dt, dev)
-        if t.numel() != numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
-    pa = (ctypes.c_int32 * n_pairs)(*pair_a)
-    pb = (ctypes.c_int32 * n_pairs)(*pair_b)
-    st = _native.load().mvm_rig_matrices(_p(K), _p(RT), pa, pb, S, C, n_pairs, _p(F), _p(proj),
-                                         _p(status), _stream(K))
-    _native.check("mvm_rig_matrices", st)
+    _check_args(dev, [(K, "K", f32, 9 * S * C, EXACT), (RT, "RT", f64, 16 * S * C, EXACT),
+                      (F, "F", f64, 9 * S * n_pairs, EXACT),
+                      (proj, "proj", f64, 12 * S * C if proj.numel() else 0, EXACT),
+                      (status, "status", i32, S, EXACT)])
+    _call("mvm_rig_matrices", _p(K), _p(RT), pa, pb, S, C, n_pairs, _p(F), _p(proj), _p(status),
+          _stream(K))
 
 
-@rig_matrices_out.register_fake
-def _(K, RT, pair_a, pair_b, F, proj, status):
-    return None
-
-
-@torch.library.custom_op("mvmatch::extend_costs_out", mutates_args=("E",))
+@_gpu_op("extend_costs_out", ("E",))
 def extend_costs_out(pts: Tensor, cam_offs: Tensor, F_ext: Tensor, match: Tensor, match_offs: Tensor,
                      count: Tensor, ext_offs: Tensor, n_cams: int, max_rows: int, E: Tensor) -> None:
     """The extension cost matrices E_d of every (capture, extra camera)
     (mvm_extend_costs)."""
-    dev = pts.device
-    if dev.type != "cuda":
-        raise ValueError("pts must be a GPU tensor (the matcher has no CPU path)")
+    dev = _gpu(pts, "pts")
     n_scenes = count.numel()
     n_ext = n_cams - 3
     if n_ext < 0 or n_cams > _native.MVM_MAX_CAMS:
         raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
     if match.dim() != 2 or match.shape[1] != 3:
         raise ValueError("match must be [cap, 3]")
-    for t, name, dt, numel in ((pts, "pts", torch.float64, 0),
-                               (cam_offs, "cam_offs", torch.int64, n_cams * n_scenes + 1),
-                               (F_ext, "F_ext", torch.float64, 27 * n_ext * n_scenes),
-                               (match, "match", torch.int32, 0),
-                               (match_offs, "match_offs", torch.int64, n_scenes + 1),
-                               (count, "count", torch.int32, n_scenes),
-                               (ext_offs, "ext_offs", torch.int64, n_ext * n_scenes + 1),
-                               (E, "E", torch.float32, 0)):
-        _require(t, name, dt, dev)
-        if numel and t.numel() != numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+    _check_args(dev, [(pts, "pts", f64, None, ANY), (cam_offs, "cam_offs", i64, n_cams * n_scenes + 1, EXACT),
+                      # no scene or no extra camera: not read
+                      (F_ext, "F_ext", f64, 27 * n_ext * n_scenes, EXACT if n_ext and n_scenes else ANY),
+                      (match, "match", i32, None, ANY),
+                      (match_offs, "match_offs", i64, n_scenes + 1, EXACT),
+                      (count, "count", i32, n_scenes, EXACT),
+                      (ext_offs, "ext_offs", i64, n_ext * n_scenes + 1, EXACT), (E, "E", f32, None, ANY)])
     if n_scenes == 0 or n_ext == 0 or max_rows == 0 or E.numel() == 0:
         return                       # no matrix has an entry: nothing to launch
-    st = _native.load().mvm_extend_costs(_p(pts), _p(cam_offs), _p(F_ext), _p(match), _p(match_offs),
-                                         _p(count), _p(ext_offs), n_scenes, n_cams, int(max_rows),
-                                         _p(E), _stream(pts))
-    _native.check("mvm_extend_costs", st)
+    _call("mvm_extend_costs", _p(pts), _p(cam_offs), _p(F_ext), _p(match), _p(match_offs), _p(count),
+          _p(ext_offs), n_scenes, n_cams, int(max_rows), _p(E), _stream(pts))
 
 
-@extend_costs_out.register_fake
-def _(pts, cam_offs, F_ext, match, match_offs, count, ext_offs, n_cams, max_rows, E):
-    return None
-
-
-@torch.library.custom_op("mvmatch::extend_select_triangulate_out",
-                         mutates_args=("views", "ext_cost", "X"))
+@_gpu_op("extend_select_triangulate_out", ("views", "ext_cost", "X"))
 def extend_select_triangulate_out(E: Tensor, ext_offs: Tensor, lsap_offs: Tensor, row_ind: Tensor,
                                   col_ind: Tensor, match: Tensor, match_offs: Tensor, count: Tensor,
                                   pts: Tensor, cam_offs: Tensor, proj: Tensor, threshold: float,
                                   views: Tensor, ext_cost: Tensor, X: Tensor) -> None:
     """Threshold + scatter of the extension's assignments and the V-view DLT
     (mvm_extend_select_triangulate).  ``X`` is in/out."""
-    dev = match.device
-    if dev.type != "cuda":
-        raise ValueError("match must be a GPU tensor (the matcher has no CPU path)")
+    dev = _gpu(match, "match")
     n_scenes = count.numel()
     if views.dim() != 2 or not 3 <= views.shape[1] <= _native.MVM_MAX_CAMS:
         raise ValueError(f"views must be [cap, C], 3 <= C <= {_native.MVM_MAX_CAMS}")
@@ -671,35 +516,23 @@ def extend_select_triangulate_out(E: Tensor, ext_offs: Tensor, lsap_offs: Tensor
     n_ext = n_cams - 3
     if match.dim() != 2 or tuple(match.shape) != (cap, 3):
         raise ValueError(f"match must be [{cap}, 3] (the rows of views)")
-    for t, name, dt, numel in ((E, "E", torch.float32, -1), (ext_offs, "ext_offs", torch.int64, n_ext * n_scenes + 1),
-                               (lsap_offs, "lsap_offs", torch.int64, n_ext * n_scenes + 1),
-                               (row_ind, "row_ind", torch.int64, -1), (col_ind, "col_ind", torch.int64, -1),
-                               (match, "match", torch.int32, 3 * cap),
-                               (match_offs, "match_offs", torch.int64, n_scenes + 1),
-                               (count, "count", torch.int32, n_scenes), (pts, "pts", torch.float64, -1),
-                               (cam_offs, "cam_offs", torch.int64, n_cams * n_scenes + 1),
-                               (proj, "proj", torch.float64, 12 * n_cams * n_scenes),
-                               (views, "views", torch.int32, n_cams * cap),
-                               (ext_cost, "ext_cost", torch.float32, n_ext * cap),
-                               (X, "X", torch.float64, 3 * cap)):
-        _require(t, name, dt, dev)
-        if numel >= 0 and t.numel() != numel:
-            raise ValueError(f"{name} holds {t.numel()} elements, expected {numel}")
+    _check_args(dev, [(E, "E", f32, None, ANY), (ext_offs, "ext_offs", i64, n_ext * n_scenes + 1, EXACT),
+                      (lsap_offs, "lsap_offs", i64, n_ext * n_scenes + 1, EXACT),
+                      (row_ind, "row_ind", i64, None, ANY), (col_ind, "col_ind", i64, None, ANY),
+                      (match, "match", i32, 3 * cap, EXACT),
+                      (match_offs, "match_offs", i64, n_scenes + 1, EXACT),
+                      (count, "count", i32, n_scenes, EXACT), (pts, "pts", f64, None, ANY),
+                      (cam_offs, "cam_offs", i64, n_cams * n_scenes + 1, EXACT),
+                      (proj, "proj", f64, 12 * n_cams * n_scenes, EXACT),
+                      (views, "views", i32, n_cams * cap, EXACT),
+                      (ext_cost, "ext_cost", f32, n_ext * cap, EXACT), (X, "X", f64, 3 * cap, EXACT)])
     if col_ind.numel() != row_ind.numel():
         raise ValueError("row_ind / col_ind differ in length")
     if n_scenes == 0 or n_ext == 0 or cap == 0:
         return                       # no row to fill: nothing to launch
-    st = _native.load().mvm_extend_select_triangulate(
-        _p(E), _p(ext_offs), _p(lsap_offs), _p(row_ind), _p(col_ind), _p(match), _p(match_offs),
-        _p(count), _p(pts), _p(cam_offs), _p(proj), n_scenes, n_cams, float(threshold), _p(views),
-        _p(ext_cost), _p(X), _stream(match))
-    _native.check("mvm_extend_select_triangulate", st)
-
-
-@extend_select_triangulate_out.register_fake
-def _(E, ext_offs, lsap_offs, row_ind, col_ind, match, match_offs, count, pts, cam_offs, proj, threshold,
-      views, ext_cost, X):
-    return None
+    _call("mvm_extend_select_triangulate", _p(E), _p(ext_offs), _p(lsap_offs), _p(row_ind), _p(col_ind),
+          _p(match), _p(match_offs), _p(count), _p(pts), _p(cam_offs), _p(proj), n_scenes, n_cams,
+          float(threshold), _p(views), _p(ext_cost), _p(X), _stream(match))
 
 
 # ---------------------------------------------------------------- plans ----
@@ -909,19 +742,28 @@ def sparse_class_bounds() -> Tuple[int, int, int]:
     return tuple(int(x.value) for x in v)
 
 
+def sparse_class(long_side, short_side, min_cols: Optional[int] = None) -> np.ndarray:
+    """Per assignment problem, given its longer and shorter side: True where
+    it is of the candidate-list class (``sparse_class_bounds``; ``min_cols``:
+    the lower bound of the long side if not the default).  The one statement
+    of that predicate on the Python side: what else a caller needs (a
+    non-empty problem, views the minima kernel takes) it adds itself."""
+    lo, hi, sh = sparse_class_bounds()
+    lo = lo if min_cols is None else int(min_cols)
+    return (long_side >= lo) & (long_side > 1024) & (long_side <= hi) & (short_side <= sh)
+
+
 def cube_free_scenes(counts: np.ndarray, min_cols: Optional[int] = None) -> np.ndarray:
     """Per scene of a (S, 3) count array: True where the cube-free association
     (triplet_minima -> linear_sum_assignment_resid -> select_triangulate_resid)
-    can take it: an empty problem, or views of <= 256 detections whose
-    flattened (N*M, P) problem is of the candidate-list class."""
-    lo, hi, sh = sparse_class_bounds()
-    lo = lo if min_cols is None else int(min_cols)
+    can take it: views of <= 256 detections (what the minima kernel takes) and
+    either an empty problem or a flattened (N*M, P) problem of the
+    candidate-list class."""
     c = np.asarray(counts, dtype=np.int64).reshape(-1, 3)
     nm, p = c[:, 0] * c[:, 1], c[:, 2]
     empty = (nm == 0) | (p == 0)
-    lng, sht = np.maximum(nm, p), np.minimum(nm, p)
-    ok = (c.max(axis=1) <= 256) & (lng >= lo) & (lng > 1024) & (lng <= hi) & (sht <= sh)
-    return empty | ok
+    ok = sparse_class(np.maximum(nm, p), np.minimum(nm, p), min_cols)
+    return (empty | ok) & (c.max(axis=1) <= 256)
 
 
 def hbm_write_probe(buf: Tensor) -> None:
@@ -929,8 +771,7 @@ def hbm_write_probe(buf: Tensor) -> None:
     if buf.device.type != "cuda" or not buf.is_contiguous():
         raise ValueError("hbm_write_probe needs a contiguous GPU tensor")
     nbytes = buf.numel() * buf.element_size() // 16 * 16
-    st = _native.load().mvm_hbm_write_probe(_p(buf), nbytes, _stream(buf))
-    _native.check("mvm_hbm_write_probe", st)
+    _call("mvm_hbm_write_probe", _p(buf), nbytes, _stream(buf))
 
 
 class LsapPlan:
@@ -978,6 +819,14 @@ class LsapPlan:
         self.short_max = int(shorts.max()) if shorts.size else 0
 
 
+def _assignment_outputs(plan: LsapPlan, dev: torch.device) -> Tuple[Tensor, Tensor, Tensor]:
+    """(row_ind i64, col_ind i64, status i32 [n]) for the solvers to write;
+    the index arrays hold max(plan.n_out, 1) entries."""
+    return (torch.empty(max(plan.n_out, 1), dtype=i64, device=dev),
+            torch.empty(max(plan.n_out, 1), dtype=i64, device=dev),
+            torch.empty(plan.n, dtype=i32, device=dev))
+
+
 def linear_sum_assignment_batched(cost: Tensor, cost_offs: Tensor, plan: LsapPlan, *,
                                   options: Optional[dict] = None,
                                   bmin8: Optional[Tuple[Tensor, Tensor, Tensor]] = None):
@@ -989,19 +838,16 @@ def linear_sum_assignment_batched(cost: Tensor, cost_offs: Tensor, plan: LsapPla
     those instead of reading every cost once more (same result)."""
     if cost.dtype != plan.dtype:
         raise ValueError(f"cost is {cost.dtype} but the plan was built for {plan.dtype}")
-    dev = cost.device
-    row_ind = torch.empty(max(plan.n_out, 1), dtype=torch.int64, device=dev)
-    col_ind = torch.empty(max(plan.n_out, 1), dtype=torch.int64, device=dev)
-    status = torch.empty(plan.n, dtype=torch.int32, device=dev)
+    row_ind, col_ind, status = _assignment_outputs(plan, cost.device)
     if bmin8 is not None and cost.dtype == torch.float32:
         torch.ops.mvmatch.lsap_solve_bmin8_out(cost, cost_offs, plan.dims, plan.ws_offs, plan.out_offs,
                                                plan.workspace, row_ind, col_ind, status, bmin8[0],
                                                bmin8[1], bmin8[2], plan.long_min, plan.long_max,
                                                plan.short_max, _opts_list(options))
-        return row_ind[:plan.n_out], col_ind[:plan.n_out], status
-    torch.ops.mvmatch.lsap_solve_out(cost, cost_offs, plan.dims, plan.ws_offs, plan.out_offs,
-                                     plan.workspace, row_ind, col_ind, status, plan.long_min,
-                                     plan.long_max, _opts_list(options), plan.short_max)
+    else:
+        torch.ops.mvmatch.lsap_solve_out(cost, cost_offs, plan.dims, plan.ws_offs, plan.out_offs,
+                                         plan.workspace, row_ind, col_ind, status, plan.long_min,
+                                         plan.long_max, _opts_list(options), plan.short_max)
     return row_ind[:plan.n_out], col_ind[:plan.n_out], status
 
 
@@ -1011,10 +857,8 @@ def lsap_sparse_stats(plan: LsapPlan, min_cols: Optional[int] = None) -> np.ndar
     scans, dense tie scans, overflowed lists, Dijkstra steps; -1 for problems
     outside the class (``min_cols``: its lower bound if not the default)."""
     lib = _native.load()
-    lo, hi, sh = sparse_class_bounds()
-    lo = lo if min_cols is None else int(min_cols)
     lng, sht = np.maximum(plan.rows, plan.cols), np.minimum(plan.rows, plan.cols)
-    cls = (lng >= lo) & (lng > 1024) & (lng <= hi) & (sht >= 1) & (sht <= sh)
+    cls = sparse_class(lng, sht, min_cols) & (sht >= 1)
     out = np.full((plan.n, 4), -1, np.int64)
     if not cls.any():
         return out
@@ -1039,10 +883,7 @@ def linear_sum_assignment_resid(plan: LsapPlan, tplan: TripletPlan, minima, *,
     if not plan.resid:
         raise ValueError("linear_sum_assignment_resid needs LsapPlan(..., resid=True)")
     bmin8, bm32 = minima                  # what triplet_minima returned (bmin8 may be empty)
-    dev = bm32.device
-    row_ind = torch.empty(max(plan.n_out, 1), dtype=torch.int64, device=dev)
-    col_ind = torch.empty(max(plan.n_out, 1), dtype=torch.int64, device=dev)
-    status = torch.empty(plan.n, dtype=torch.int32, device=dev)
+    row_ind, col_ind, status = _assignment_outputs(plan, bm32.device)
     torch.ops.mvmatch.lsap_solve_resid_out(plan.dims, plan.ws_offs, plan.out_offs, plan.workspace,
                                            row_ind, col_ind, status, bmin8, tplan.bmin8_offs, bm32,
                                            tplan.bm32_offs, tplan.segs, tplan.workspace, tplan.max_n,
@@ -1085,23 +926,25 @@ def triangulate_dlt(proj: Tensor, pts2d: Tensor, set_of_point: Optional[Tensor] 
     return X
 
 
+def _select_outputs(row_ind: Tensor, lsap_offs: Tensor, dev: torch.device):
+    """(match i32 [cap, 3], cost f32 [cap], X f64 [cap, 3], count i32 [S]) for
+    the select kernels to write: one row per assigned pair."""
+    cap = int(row_ind.numel())
+    return (torch.empty((cap, 3), dtype=i32, device=dev), torch.empty(cap, dtype=f32, device=dev),
+            torch.empty((cap, 3), dtype=f64, device=dev),
+            torch.empty(int(lsap_offs.numel()) - 1, dtype=i32, device=dev))
+
+
 def select_triangulate(cube: Tensor, cube_offs: Tensor, cam_offs: Tensor, lsap_offs: Tensor,
                        row_ind: Tensor, col_ind: Tensor, pts: Tensor, proj: Tensor,
                        threshold: float):
     """Filter + stable cost sort + DLT of every scene's assignment (device).
     -> (match i32 [cap, 3], cost f32 [cap], X f64 [cap, 3], count i32 [S]); scene
     s's matches are rows ``lsap_offs[s] : lsap_offs[s] + count[s]``."""
-    dev = cube.device
-    cap = int(row_ind.numel())
-    n_scenes = int(lsap_offs.numel()) - 1
-    match = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-    cost = torch.empty(cap, dtype=torch.float32, device=dev)
-    X = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-    count = torch.empty(n_scenes, dtype=torch.int32, device=dev)
+    outs = _select_outputs(row_ind, lsap_offs, cube.device)
     torch.ops.mvmatch.select_triangulate_out(cube, cube_offs, cam_offs, lsap_offs, row_ind,
-                                             col_ind, pts, proj.contiguous(), float(threshold),
-                                             match, cost, X, count)
-    return match, cost, X, count
+                                             col_ind, pts, proj.contiguous(), float(threshold), *outs)
+    return outs
 
 
 def select_triangulate_resid(tplan: TripletPlan, cam_offs: Tensor, lsap_offs: Tensor,
@@ -1109,17 +952,11 @@ def select_triangulate_resid(tplan: TripletPlan, cam_offs: Tensor, lsap_offs: Te
                              threshold: float):
     """select_triangulate for a ``triplet_minima(..., tplan)`` batch: each
     assigned entry recomputed from the residuals in ``tplan.workspace``."""
-    dev = pts.device
-    cap = int(row_ind.numel())
-    n_scenes = int(lsap_offs.numel()) - 1
-    match = torch.empty((cap, 3), dtype=torch.int32, device=dev)
-    cost = torch.empty(cap, dtype=torch.float32, device=dev)
-    X = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-    count = torch.empty(n_scenes, dtype=torch.int32, device=dev)
+    outs = _select_outputs(row_ind, lsap_offs, pts.device)
     torch.ops.mvmatch.select_triangulate_resid_out(tplan.workspace, tplan.max_n, cam_offs, lsap_offs,
                                                    row_ind, col_ind, pts, proj.contiguous(),
-                                                   float(threshold), match, cost, X, count)
-    return match, cost, X, count
+                                                   float(threshold), *outs)
+    return outs
 
 
 def _h2d_rig(Ks: np.ndarray, RTs: np.ndarray, device: torch.device) -> Tuple[Tensor, Tensor]:

@@ -300,6 +300,44 @@ def test_match_captures_cube_free_equals_keep_cube(cuda, parts):
         assert free.any() and not free.all()
 
 
+def test_empty_scene_with_wide_view_keeps_the_cube(cuda):
+    """An empty scene (a view without detections) with a view above the 256
+    detections the minima kernel takes is not cube-free: next to the smallest
+    non-empty scene of the class, (n, n, 1) with n*n the class's lower bound,
+    the batch once went whole to mvm_triplet_minima, which refused its max_n
+    of 300.  It now splits, and equals keep_cube=True bit for bit."""
+    from bpc_baseline_amd import ops
+    from bpc_baseline_amd.inference.batch_match import match_captures
+    from bpc_baseline_amd.synth import make_capture
+    lo, _, _ = ops.sparse_class_bounds()
+    n = int(np.ceil(np.sqrt(lo)))
+    counts = [(0, 300, 50), (n, n, 1)]
+    assert ops.cube_free_scenes(np.array(counts)).tolist() == [False, True]
+    assert not ops.cube_free_scenes(np.array([(n - 1, n, 1)]))[0]      # one detection fewer: below the class
+    rng = np.random.default_rng(33)
+    boxes, Ks, RTs = [], [], []
+    for c in counts:
+        K, RT, dets = make_capture(rng, 3, list(c))
+        boxes += [np.asarray([d["bbox"] for d in dets[cam]], np.float32).reshape(-1, 4) for cam in range(3)]
+        Ks.append(np.stack(K))
+        RTs.append(np.stack(RT))
+    img_offs = np.zeros(7, np.int64)
+    np.cumsum([len(b) for b in boxes], out=img_offs[1:])
+    n_box = int(img_offs[-1])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+    args = (t(np.concatenate(boxes)), t(np.ones(n_box, np.float32)), t(np.zeros(n_box, np.float32)),
+            t(img_offs), np.stack(Ks), np.stack(RTs))
+    # threshold inf: every assigned pair is a match, so there is one to compare
+    a = match_captures(*args, matching_threshold=np.inf)
+    b = match_captures(*args, matching_threshold=np.inf, keep_cube=True)
+    assert np.diff(a.cam_offs).reshape(-1, 3).tolist() == [list(c) for c in counts]
+    assert a.count.tolist() == b.count.tolist() == [0, 1] and np.array_equal(a.offs, b.offs)
+    k = slice(int(a.offs[1]), int(a.offs[1]) + 1)
+    assert np.array_equal(a.match[k].cpu().numpy(), b.match[k].cpu().numpy())
+    assert np.array_equal(a.cost[k].cpu().numpy().view(np.int32), b.cost[k].cpu().numpy().view(np.int32))
+    assert np.array_equal(a.X[k].cpu().numpy().view(np.int64), b.X[k].cpu().numpy().view(np.int64))
+
+
 @pytest.mark.parametrize("n", [64, 100, 256])
 def test_resid_lists_hold_on_small_rows(cuda, n):
     """Every lane of the list kernel holds block keys whatever a row's key
