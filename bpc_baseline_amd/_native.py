@@ -187,6 +187,10 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, _vp,            # dense_offs, scene, views, n_views, cost (out)
         _vp, _vp, _vp, _vp, _vp,            # ext_cost (may be NULL), X, boxes, cent, reproj (out)
         _vp]),                              # stream
+    "mvm_prune_views_triangulate": (ctypes.c_int, [
+        _vp, _vp, _i32, _i32,               # match_offs, count, n_scenes, n_cams
+        _vp, _vp, _vp, ctypes.c_double,     # pts, cam_offs, proj, gate
+        _vp, _vp, _vp, _vp, _vp]),          # views, ext_cost, X (in/out), pruned (out), stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

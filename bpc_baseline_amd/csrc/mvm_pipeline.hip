@@ -441,6 +441,19 @@ __global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
 constexpr int kCompactThreads = 256;
 constexpr int kCompactScenes = kCompactThreads / 64;
 
+// The reprojection residual of X in one view (include/mvmatch.h,
+// mvm_compact_matches_views): p the view's row-major 3x4 P, (cx, cy) its
+// centroid.  Every product and sum is rounded on its own (this file's fp
+// contract(off)), the divisions and the square root are IEEE.
+__device__ __forceinline__ double reproj_residual(const double *p, double X0, double X1, double X2,
+                                                  double cx, double cy) {
+    const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
+    const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
+    const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
+    const double du = h0 / h2 - cx, dv = h1 / h2 - cy;
+    return sqrt(du * du + dv * dv);
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
     const int32_t *__restrict__ match, const float *__restrict__ cost, const double *__restrict__ X,
@@ -556,12 +569,7 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
                         cent_out[2 * o] = cx;
                         cent_out[2 * o + 1] = cy;
                     }
-                    const double *p = P + 12 * c;
-                    const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
-                    const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
-                    const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
-                    const double du = h0 / h2 - cx, dv = h1 / h2 - cy;
-                    reproj_out[o] = sqrt(du * du + dv * dv);
+                    reproj_out[o] = reproj_residual(P + 12 * c, X0, X1, X2, cx, cy);
                 } else {
                     if (VEC) {
                         reinterpret_cast<int4 *>(boxes_out)[o] = make_int4(-1, -1, -1, -1);
@@ -577,6 +585,121 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
             }
         }
         nviews_out[r] = kept;
+    }
+}
+
+// ------------------------------------------------- view pruning ----
+// mvm_prune_views_triangulate: per match of a C-camera batch,
+// drop the extra views whose reprojection residual exceeds `gate`, the worst
+// one at a time, and triangulate again over what is left after every drop.
+// The shape of compact_matches_views_kernel: one wave per capture (its index
+// a scalar, so the extra cameras' P and the capture's cam_offs are scalar
+// loads ahead of the match loop), four captures per workgroup, lanes striding
+// over the capture's matches; no LDS, no barrier.  The kept set is a bit
+// mask; the worst view is chosen over compile-time camera slots under the
+// mask's bit, and the DLT gathers by constant slot (extend_dlt), so no
+// register array is indexed by a runtime value.  A row that drops nothing is
+// not written (its `pruned` word is 0).
+constexpr int kPruneSlots = MVM_MAX_CAMS - 3;    // the extra cameras 3 .. 7
+
+__global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
+    const int64_t *__restrict__ match_offs, const int32_t *__restrict__ count,
+    const double *__restrict__ pts, const int64_t *__restrict__ cam_offs,
+    const double *__restrict__ proj, double gate, int32_t n_scenes, int32_t n_cams, int32_t *views,
+    float *ext_cost, double *X, int32_t *__restrict__ pruned) {
+    const int lane = threadIdx.x % 64;
+    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
+                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    if (s >= n_scenes) return;
+    const int64_t mo = match_offs[s];
+    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
+    const int n_ext = n_cams - 3;
+    const int64_t *co_s = cam_offs + s * n_cams;
+    const double *proj_s = proj + s * n_cams * 12;
+    // n_cams >= 4: co_s[3] closes the third seed view
+    const int64_t seed_n[3] = {co_s[1] - co_s[0], co_s[2] - co_s[1], co_s[3] - co_s[2]};
+    int64_t co[kPruneSlots], view_n[kPruneSlots];
+    double P[12 * kPruneSlots];
+#pragma unroll
+    for (int e = 0; e < kPruneSlots; ++e) {
+        if (e < n_ext) {
+            co[e] = co_s[3 + e];
+            view_n[e] = co_s[3 + e + 1] - co[e];     // cam_offs holds C S + 1 entries
+#pragma unroll
+            for (int k = 0; k < 12; ++k) P[12 * e + k] = proj_s[12 * (3 + e) + k];
+        }
+    }
+    for (int64_t w = lane; w < n; w += 64) {
+        const int64_t row = mo + w;
+        int32_t *vw = views + row * n_cams;
+        // extend_select_triangulate_kernel's `ok`: a seed outside its view leaves the row
+        // alone; so does an extra-view entry that is neither negative (no
+        // detection) nor a detection of its view -- no index is used unchecked
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ok &= vw[c] >= 0 && vw[c] < seed_n[c];
+        int32_t ve[kPruneSlots];
+#pragma unroll
+        for (int e = 0; e < kPruneSlots; ++e) {
+            if (e < n_ext) {
+                ve[e] = vw[3 + e];
+                ok &= ve[e] < view_n[e];
+            }
+        }
+        uint32_t mask = 7u, dropped = 0u;
+        double cx[kPruneSlots], cy[kPruneSlots];
+#pragma unroll
+        for (int e = 0; e < kPruneSlots; ++e) {
+            if (e < n_ext && ok && ve[e] >= 0) {
+                mask |= 1u << (3 + e);
+                cx[e] = pts[2 * (co[e] + ve[e])];
+                cy[e] = pts[2 * (co[e] + ve[e]) + 1];
+            }
+        }
+        if (mask != 7u) {
+            double X0 = X[3 * row], X1 = X[3 * row + 1], X2 = X[3 * row + 2];
+            for (int pass = 0; pass < n_ext; ++pass) {
+                // the worst candidate: NaN above every number, then the largest
+                // residual, ties to the lowest camera (ascending slots, strict >)
+                int worst = -1;
+                double worst_r = 0.0;
+                bool worst_nan = false;
+#pragma unroll
+                for (int e = 0; e < kPruneSlots; ++e) {
+                    if ((mask >> (3 + e)) & 1u) {
+                        const double r = reproj_residual(P + 12 * e, X0, X1, X2, cx[e], cy[e]);
+                        if (!(r <= gate)) {
+                            const bool r_nan = r != r;
+                            if (worst < 0 || (!worst_nan && (r_nan || r > worst_r))) {
+                                worst = 3 + e;
+                                worst_r = r;
+                                worst_nan = r_nan;
+                            }
+                        }
+                    }
+                }
+                if (worst < 0) break;
+                mask &= ~(1u << worst);
+                dropped |= 1u << worst;
+                vw[worst] = -1;
+                ext_cost[row * n_ext + (worst - 3)] = INFINITY;
+                double out[3];
+                switch (__builtin_popcount(mask)) {
+                    case 3: extend_dlt<3>(proj_s, pts, co_s, vw, mask, out); break;
+                    case 4: extend_dlt<4>(proj_s, pts, co_s, vw, mask, out); break;
+                    case 5: extend_dlt<5>(proj_s, pts, co_s, vw, mask, out); break;
+                    case 6: extend_dlt<6>(proj_s, pts, co_s, vw, mask, out); break;
+                    default: extend_dlt<7>(proj_s, pts, co_s, vw, mask, out); break;
+                }
+                X0 = out[0], X1 = out[1], X2 = out[2];
+            }
+            if (dropped) {
+                X[3 * row] = X0;
+                X[3 * row + 1] = X1;
+                X[3 * row + 2] = X2;
+            }
+        }
+        pruned[row] = (int32_t)dropped;
     }
 }
 
@@ -850,6 +973,31 @@ int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
             cent_out_dev, reproj_out_dev);
     });
     return mvm_check_launch("compact_matches_views_kernel");
+}
+
+int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *count_dev,
+                                int32_t n_scenes, int32_t n_cams, const double *pts_dev,
+                                const int64_t *cam_offs_dev, const double *proj_dev, double gate,
+                                int32_t *views_dev, float *ext_cost_dev, double *X_dev,
+                                int32_t *pruned_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    if (n_cams < 4 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [4, %d]", n_cams, MVM_MAX_CAMS);
+    if (!(gate >= 0.0))                  // NaN included
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "gate=%g: a number >= 0 (or +inf) required", gate);
+    if (const int st = mvm_require_ptrs({{match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
+                                         {pts_dev, "pts_dev"},               {cam_offs_dev, "cam_offs_dev"},
+                                         {proj_dev, "proj_dev"},             {views_dev, "views_dev"},
+                                         {ext_cost_dev, "ext_cost_dev"},     {X_dev, "X_dev"},
+                                         {pruned_dev, "pruned_dev"}}))
+        return st;
+    const int grid = (int)(((int64_t)n_scenes + kCompactScenes - 1) / kCompactScenes);
+    prune_views_kernel<<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, gate, n_scenes, n_cams, views_dev,
+        ext_cost_dev, X_dev, pruned_dev);
+    return mvm_check_launch("prune_views_kernel");
 }
 
 int mvm_pack_detections(const float *boxes_dev, const float *conf_dev, const float *cls_dev,

@@ -34,7 +34,7 @@ from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, ops_views
 from .utils.camera_utils import (fundamental_matrices_batched, pinhole_intrinsics, projection_matrices,
                                  rig_matrices)
 
@@ -130,11 +130,17 @@ class MatchBatch:
     # the projection matrices X was triangulated with, all C cameras (what
     # the table's reprojection residuals are measured against)
     proj: Optional[torch.Tensor] = None           # float64 [S, C, 3, 4]
+    # match_captures(reproj_gate=G): bit d set where the extra
+    # view of camera d was dropped for its reprojection residual (0 in every
+    # row of a three-camera batch); None without a gate
+    pruned: Optional[torch.Tensor] = None         # int32 [cap]
 
     def host(self) -> dict:
-        """One D2H copy of everything ``predictions`` reads."""
+        """One D2H copy of everything ``predictions`` reads (and ``pruned``
+        when the batch has it)."""
         if not hasattr(self, "_host"):
             keys = ("match", "cost", "X", "pts", "boxes") + (("views",) if self.n_cams > 3 else ())
+            keys += ("pruned",) if self.pruned is not None else ()
             self._host = {k: getattr(self, k).cpu().numpy() for k in keys}
         return self._host
 
@@ -291,7 +297,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    keep_cube: bool = False, timings: Optional[dict] = None,
                    F: Optional[torch.Tensor] = None,
                    proj: Optional[torch.Tensor] = None, rig: str = "host",
-                   n_cams: int = 3) -> MatchBatch:
+                   n_cams: int = 3, reproj_gate: Optional[float] = None) -> MatchBatch:
     """Detect-packing + matching + triangulation of S 3-camera captures.
 
     ``boxes`` f32 [n, 4] xyxy, ``conf``/``cls`` f32 [n]: the detector outputs
@@ -332,9 +338,20 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     The result keeps ``proj`` (device, [S, C, 3, 4], all C cameras), computed
     here or passed in: what ``MatchBatch.table`` measures the reprojection
     residuals against.
+
+    ``reproj_gate`` = G pixels, 0 <= G <= +inf (None, the default: off,
+    nothing launched): after the extension, every match drops the extra views
+    whose reprojection residual is not <= G, the worst first and one at a
+    time, and is triangulated again over the views left after each drop
+    (``ops_views.prune_views``; on the device, no further
+    device -> host copy).  A dropped view reads -1 in ``views`` and +inf in
+    ``ext_cost``; the result's ``pruned`` holds bit d where camera d was
+    dropped.  Cameras 0-2, the matches, their costs, order and counts never
+    change.  With ``n_cams=3`` the gate is accepted and ``pruned`` is zeros.
     """
     C = _check_n_cams(n_cams)
     _check_rig(rig)
+    gate = None if reproj_gate is None else ops_views._check_gate(reproj_gate)
     if rig != "host" and (F is not None or proj is not None):
         raise TypeError(f"F / proj cannot be passed with rig={rig!r}: that path computes them")
     dev = boxes.device
@@ -438,14 +455,20 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     if np.any(bad):
         _raise_failed(bad)
     mark("results D2H")
-    views = ext_cost = None
+    views = ext_cost = pruned = None
     if C > 3:
         views, ext_cost = _extend(full, res, count_h, S, C, threshold, mark)
+    if gate is not None:
+        pruned = torch.zeros(int(res.match.shape[0]), dtype=torch.int32, device=dev)
+        if C > 3:
+            ops_views.prune_views(views, ext_cost, res.X, res.offs_dev, res.count, full.pts, full.cam_offs,
+                                  full.proj, gate, C, out=pruned)
+            mark("prune")
     return MatchBatch(match=res.match, cost=res.cost, X=res.X, count=count_h, offs=res.offs_host,
                       pts=full.pts, boxes=boxes_int, cam_offs=full.cam_offs_host,
                       cube=res.cube if keep_cube else None, offs_dev=res.offs_dev, count_dev=res.count,
                       cam_offs_dev=full.cam_offs, views=views, ext_cost=ext_cost, n_cams=C,
-                      proj=full.proj.reshape(S, C, 3, 4))
+                      proj=full.proj.reshape(S, C, 3, 4), pruned=pruned)
 
 
 def _extend(full: _Rig, res: _Chain, count_h, S, C, threshold, mark):

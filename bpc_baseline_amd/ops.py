@@ -150,12 +150,18 @@ def _scene_rows(pts: Tensor, cam_offs: Tensor, F: Tensor, n_views: int, n_mats: 
                  (F, "F", f64, 9 * n_mats, EXACT)]
 
 
-def _gpu_op(name: str, mutates_args):
+def _fake_none(*args, **kwargs) -> None:
+    """The fake of every op here: they return None (nothing to allocate or shape)."""
+    return None
+
+
+def _gpu_op(name: str, mutates_args, namespace: str = "mvmatch"):
     """``torch.library.custom_op("mvmatch::<name>")`` for an op that returns
-    None, so one fake serves every op (nothing to allocate or shape)."""
+    None, so one fake serves every op (nothing to allocate or shape).
+    ``namespace``: for a module that registers its ops beside this one's."""
     def wrap(fn):
-        op = torch.library.custom_op(f"mvmatch::{name}", mutates_args=mutates_args)(fn)
-        op.register_fake(lambda *args, **kwargs: None)
+        op = torch.library.custom_op(f"{namespace}::{name}", mutates_args=mutates_args)(fn)
+        op.register_fake(_fake_none)
         return op
     return wrap
 

@@ -46,6 +46,8 @@ extern "C" {
                             ABI 8 (no existing signature or struct changed) */
 #define MVM_HAS_VIEW_TABLE 1 /* mvm_compact_matches_views: an addition to ABI 8 (no existing
                                 signature or struct changed) */
+#define MVM_HAS_VIEW_PRUNE 1 /* mvm_prune_views_triangulate: an addition to ABI 8 (no existing
+                                signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -672,6 +674,41 @@ int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
                               int32_t *views_out_dev, int32_t *n_views_out_dev, float *cost_out_dev,
                               float *ext_cost_out_dev, double *X_out_dev, int32_t *boxes_out_dev,
                               double *cent_out_dev, double *reproj_out_dev, mvm_stream_t stream);
+
+/*
+ * Pruning of extra views by reprojection residual, with re-triangulation, for
+ * a C-camera batch, 4 <= C <= MVM_MAX_CAMS (an addition to ABI 8, announced by
+ * MVM_HAS_VIEW_PRUNE).  In/out, as mvm_extend_select_triangulate left them:
+ * views_dev int32 [.., C], ext_cost_dev f32 [.., C-3], X_dev f64 [.., 3], with
+ * capture s's count_dev[s] matches at rows match_offs_dev[s] + w (never more
+ * rows than match_offs[s+1] - match_offs[s]); pts_dev / cam_offs_dev the
+ * C-camera CSR, proj_dev f64 [S, C, 3, 4].  gate: pixels, 0 <= gate <= +inf.
+ * For match w, with the kept set K = {0, 1, 2} + {d >= 3 : views[w][d] >= 0}:
+ *   1. X = the DLT over K in ascending camera order (mvm_triangulate_dlt's);
+ *      on the first pass, nothing dropped yet, the value X_dev holds;
+ *   2. r_d, d in K, d >= 3: the reprojection residual of
+ *      mvm_compact_matches_views, in that order of operations;
+ *   3. the candidates are the d with !(r_d <= gate) (a NaN residual is one);
+ *      none: stop.  Else the worst is dropped -- NaN above every number, then
+ *      the largest r_d, ties to the lowest camera: views[w][d] = -1,
+ *      ext_cost[w][d-3] = +inf, bit d of pruned_dev[w] set;
+ *   4. back to 1 (at most C-3 drops).
+ * Cameras 0-2 are never dropped; a detection a drop releases is not offered
+ * to another match.  A row that drops nothing has views / ext_cost / X not
+ * written and pruned_dev[w] = 0; so has a row whose (i, j, k) are outside
+ * their views, or with an extra-view entry that is neither negative (no
+ * detection) nor a detection of its view: no index is used unchecked.
+ * pruned_dev int32 [..] is written for the count_dev[s] rows of every
+ * capture; no row outside them is written in any array.
+ * One launch on `stream`, a wave per capture; no allocation, copy or
+ * synchronisation.  n_scenes == 0 launches nothing.  A NULL pointer, n_cams
+ * outside 4..MVM_MAX_CAMS, a NaN or a negative gate is refused before the launch.
+ */
+int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *count_dev,
+                                int32_t n_scenes, int32_t n_cams, const double *pts_dev,
+                                const int64_t *cam_offs_dev, const double *proj_dev, double gate,
+                                int32_t *views_dev, float *ext_cost_dev, double *X_dev,
+                                int32_t *pruned_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

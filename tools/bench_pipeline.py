@@ -8,6 +8,9 @@ stage "F+P host" becomes "F+P device"); the static-rig line is the floor either 
 --cams C (4..8): captures of C cameras from make_capture, matched with
 match_captures(n_cams=C); --first-three matches only cameras 0-2
 of the same captures, the three-camera line the extension is measured against.
+--reproj-gate G (with --cams C > 3): match_captures(reproj_gate=G) (DESIGN
+§3.15); the stage "prune" and the number of matches that dropped a view are
+in the line.
 """
 import argparse
 import json
@@ -80,6 +83,8 @@ def main_wide(args):
         Ks, RTs = np.ascontiguousarray(Ks[:, :3]), np.ascontiguousarray(RTs[:, :3])
     else:
         kw["n_cams"] = C
+        if args.reproj_gate is not None:
+            kw["reproj_gate"] = args.reproj_gate
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     inp = (t(boxes), t(conf), t(cls), t(offs), Ks, RTs)
     for _ in range(args.warmup):
@@ -99,8 +104,11 @@ def main_wide(args):
            "value": args.captures / dt, "unit": "captures/s", "ms_per_batch": dt * 1e3,
            "config": {"captures": args.captures, "dets_per_view": args.dets, "cams": C,
                       "matched_cams": 3 if args.first_three else C, "keep_cube": args.keep_cube,
-                      "rig": args.rig},
+                      "rig": args.rig, **({"reproj_gate": kw["reproj_gate"]} if "reproj_gate" in kw else {})},
            "matches": int(res.count.sum()), "stage_ms_synchronised": stages}
+    if res.pruned is not None:
+        out["prune_ms_synchronised"] = stages.get("prune")
+        out["matches_that_dropped_a_view"] = int((res.pruned != 0).sum())
     if not args.first_three:
         v = res.views.cpu().numpy()
         keep = np.concatenate([np.arange(o, o + n) for o, n in zip(res.offs[:-1], res.count)]
@@ -116,6 +124,8 @@ def main():
                          "match_captures(n_cams=C) (DESIGN §3.14)")
     ap.add_argument("--first-three", action="store_true",
                     help="with --cams C > 3: match cameras 0-2 of the same captures only")
+    ap.add_argument("--reproj-gate", type=float, default=None,
+                    help="with --cams C > 3: match_captures(reproj_gate=G), pixels (DESIGN §3.15)")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -129,6 +139,8 @@ def main():
     ap.add_argument("--rig", choices=("host", "device"), default="host",
                     help="where match_captures computes F and P (DESIGN §3.13)")
     args = ap.parse_args()
+    if args.reproj_gate is not None and (args.cams == 3 or args.first_three):
+        ap.error("--reproj-gate needs --cams C > 3 without --first-three (it acts on the extra views)")
     if args.cams > 3:
         return main_wide(args)
     dev = torch.device("cuda", 0)
