@@ -24,8 +24,7 @@ thread_local char g_err[512];
 __global__ __launch_bounds__(kThreads) void write_probe_kernel(f32x4 *dst, size_t n16, float val) {
     constexpr int kPerLane = 2;
     const f32x4 v = {val, val, val, val};
-    const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
-    const uint32_t blk = x * q + min(x, r) + blockIdx.x / 8;   // dispatch puts block b on XCD b % 8
+    const uint32_t blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
     const size_t base = (size_t)blk * (kPerLane * kThreads) + threadIdx.x;
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {

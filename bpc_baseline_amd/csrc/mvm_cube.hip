@@ -28,21 +28,157 @@ namespace {
 
 constexpr int kTripletRowsPerWave = 8;   // generic kernel: 32 (i, j) rows per workgroup
 
-// --------------------------------------------------------- triplet kernel ----
-struct CubeArgs {
+// ---------------------------------------------------- kernel arguments ----
+// What the kernels of a launch read and write, filled once (cube_launch,
+// mvm_triplet_minima); each kernel's Args adds its own geometry.
+struct CubeIn {
+    const double *pts;
     const int64_t *cam_offs;    // [S*3 + 1]
-    const double *e;            // fp64 pair matrices (e12, e13, e23 per scene)
-    int64_t mat_stride;         // elements between consecutive matrices
-    int64_t ld;                 // row stride of every matrix (multiple of 4)
+    const double *F;            // [S*3, 9]: F12, F13, F23
+};
+struct CubeOut {
     const int64_t *cube_offs;
     const int64_t *row_offs;
     float *cube;
     int32_t *argmin;
     float *minval;
-    int32_t i_count;            // max_n (grid i extent)
-    int32_t j_blocks;
 };
 
+// the workspace kernels (triplet_kernel, triplet_tile_kernel)
+struct CubeArgs : CubeOut {
+    const int64_t *cam_offs;    // [S*3 + 1]
+    const double *e;            // fp64 pair matrices (e12, e13, e23 per scene)
+    int64_t mat_stride;         // elements between consecutive matrices
+    int64_t ld;                 // row stride of every matrix (multiple of 4)
+    int32_t j_blocks;
+    int32_t i_blocks;           // triplet_kernel: max_n (one i row per workgroup)
+};
+
+// ------------------------------------------------- shared device helpers ----
+// Scene s of the batch: the first detection of its three views and their sizes
+struct Scene {
+    int64_t c0, c1, c2;
+    int N, M, P;
+};
+__device__ __forceinline__ Scene scene_of(const int64_t *cam_offs, int s) {
+    const int64_t *co = cam_offs + 3 * (int64_t)s;
+    const int64_t c0 = co[0], c1 = co[1], c2 = co[2];
+    return {c0, c1, c2, (int)(c1 - c0), (int)(c2 - c1), (int)(co[3] - c2)};
+}
+// the scene's fundamental matrix of pair p: 0 F12, 1 F13, 2 F23
+__device__ __forceinline__ const double *scene_F(const double *F, int s, int p) {
+    return F + (3 * (int64_t)s + p) * 9;
+}
+
+struct LineRec {
+    double l0, l1, l2;
+    double deg;                 // 1.0: degenerate line (9999 sentinel)
+};
+
+__device__ __forceinline__ double pair_e(const LineRec &col, const LineRec &row, double rx,
+                                         double ry, double cx, double cy) {
+    const double d1 = col.deg != 0.0 ? kSentinel : line_dist(col.l0, col.l1, col.l2, rx, ry);
+    const double d2 = row.deg != 0.0 ? kSentinel : line_dist(row.l0, row.l1, row.l2, cx, cy);
+    return 0.5 * (d1 + d2);                                                       // :28
+}
+
+__device__ __forceinline__ void load_f(const double *F, double f[9]) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) f[q] = F[q];
+}
+
+// the epipolar line of (x, y): F @ p (IS_ROW) or F.T @ p
+template <bool IS_ROW>
+__device__ __forceinline__ LineRec line_rec(const double f[9], double x, double y) {
+    LineRec l;
+    const bool deg = IS_ROW ? row_line(f, x, y, l.l0, l.l1, l.l2) : col_line(f, x, y, l.l0, l.l1, l.l2);
+    l.deg = deg ? 1.0 : 0.0;
+    return l;
+}
+
+// A detection with its lines under two matrices (the tiles' prologues: a
+// view-0 row under F13 and F12, a view-1 row under F12.T and F23, a view-2
+// column under F13.T and F23.T); all zeros when !valid.
+struct LinePair {
+    LineRec a, b;
+    double x, y;
+    __device__ __forceinline__ bool deg() const { return (a.deg != 0.0) || (b.deg != 0.0); }
+};
+template <bool A_IS_ROW, bool B_IS_ROW>
+__device__ __forceinline__ LinePair line_pair(const double *pts, int64_t index, bool valid,
+                                              const double *Fa, const double *Fb) {
+    LinePair p{{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, 0.0, 0.0};
+    if (valid) {
+        double f[9];
+        p.x = pts[2 * index];
+        p.y = pts[2 * index + 1];
+        load_f(Fa, f);
+        p.a = line_rec<A_IS_ROW>(f, p.x, p.y);
+        load_f(Fb, f);
+        p.b = line_rec<B_IS_ROW>(f, p.x, p.y);
+    }
+    return p;
+}
+
+// a lane's four e13 from an LDS row, 16-byte aligned: two 16-byte reads
+__device__ __forceinline__ void load4_lds(const double *p, double out[4]) {
+    const f64x2 lo = *reinterpret_cast<const f64x2 *>(p);
+    const f64x2 hi = *reinterpret_cast<const f64x2 *>(p + 2);
+    out[0] = lo.x; out[1] = lo.y; out[2] = hi.x; out[3] = hi.y;
+}
+
+// A tile's e12 [IB][KJ] into LDS from its rows' and columns' lines and points
+// (pair: row_safe's residual; rows >= ni and columns from M on: zeros).
+// Returns whether every value this thread wrote is <= kTameResidual.
+template <int IB, int KJ, typename Pair>
+__device__ __forceinline__ bool fill_e12(double (&s12)[IB][KJ], const LineRec (&c12)[KJ],
+                                         const LineRec (&r12)[IB], const double (&p0)[IB][2],
+                                         const double (&p1)[KJ][2], int ni, int jw0, int M, Pair pair) {
+    bool tame = true;
+    for (int x = threadIdx.x; x < IB * KJ; x += kThreads) {
+        const int r = x / KJ, jj = x % KJ;
+        const double e = (r < ni && jw0 + jj < M)
+                             ? pair(c12[jj], r12[r], p0[r][0], p0[r][1], p1[jj][0], p1[jj][1])
+                             : 0.0;
+        s12[r][jj] = e;
+        tame &= e <= kTameResidual;
+    }
+    return tame;
+}
+
+// The row step's arithmetic, one (i, j) row of a lane's KPL k: the sums
+// (e12 + e13) + e23 (:81) and their thirds.  Returns whether every third is
+// RN(sum / 3) (FAST: the tile's residuals are tame, nothing to test).
+template <int KPL, bool FAST>
+__device__ __forceinline__ bool row_thirds(double v12, const double (&a13)[KPL], const double (&a23)[KPL],
+                                           double (&sum)[KPL], double (&q0)[KPL]) {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < KPL; ++q) {
+        sum[q] = (v12 + a13[q]) + a23[q];
+        q0[q] = third_q(sum[q]);
+        if (!FAST) ok &= third_ok(q0[q]);
+    }
+    return ok;
+}
+
+// ... and its exact values: the IEEE division only when some lane of the wave
+// needs it (`divide` is uniform)
+template <int KPL>
+__device__ __forceinline__ void row_exact(const double (&sum)[KPL], const double (&q0)[KPL], bool divide,
+                                          float (&v)[KPL]) {
+    double qq[KPL];
+#pragma unroll
+    for (int q = 0; q < KPL; ++q) qq[q] = q0[q];
+    if (divide) {
+#pragma unroll
+        for (int q = 0; q < KPL; ++q) qq[q] = third_ok(q0[q]) ? q0[q] : sum[q] / 3.0;
+    }
+#pragma unroll
+    for (int q = 0; q < KPL; ++q) v[q] = (float)qq[q];
+}
+
+// --------------------------------------------------------- triplet kernel ----
 // ((e12 + e13) + e23) / 3 -> float32  (epipolar_matching.py:78-81, :96)
 __device__ __forceinline__ double triple_cost(double e12, double e13, double e23) {
     return ((e12 + e13) + e23) / 3.0;
@@ -55,12 +191,10 @@ __global__ __launch_bounds__(kThreads) void triplet_kernel(CubeArgs args) {
     const int lane = t % kWave;
     const int jb = (int)(blockIdx.x % (uint32_t)args.j_blocks);
     const int si = (int)(blockIdx.x / (uint32_t)args.j_blocks);
-    const int s = si / args.i_count;
-    const int i = si - s * args.i_count;
-    const int64_t o1 = args.cam_offs[3 * (int64_t)s];
-    const int N = (int)(args.cam_offs[3 * (int64_t)s + 1] - o1);
-    const int M = (int)(args.cam_offs[3 * (int64_t)s + 2] - args.cam_offs[3 * (int64_t)s + 1]);
-    const int P = (int)(args.cam_offs[3 * (int64_t)s + 3] - args.cam_offs[3 * (int64_t)s + 2]);
+    const int s = si / args.i_blocks;
+    const int i = si - s * args.i_blocks;
+    const Scene sc = scene_of(args.cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     const int j0 = jb * kWaves * RPW + wave * RPW;
     if (i >= N || j0 >= M) return;   // uniform over the wave (no barriers below)
 
@@ -215,21 +349,8 @@ __device__ __forceinline__ void empty_k_rows(int32_t *argmin, float *minval, int
 // issued after a row store waits for that store's acknowledgement, so loads
 // inside a store-streaming loop stall it.
 
-struct Cube3Args {
-    const int64_t *cam_offs;
-    const double *e;
-    int64_t mat_stride;
-    int64_t ld;
-    const int64_t *cube_offs;
-    const int64_t *row_offs;
-    float *cube;
-    int32_t *argmin;
-    float *minval;
-    int32_t j_blocks, i_blocks;
-};
-
 template <int kCubeIB, int kCubeRPW>   // i rows per tile, j rows per wave
-__global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) {
+__global__ __launch_bounds__(kThreads) void triplet_tile_kernel(CubeArgs args) {
     __shared__ __attribute__((aligned(16))) double s13[kCubeIB][kChunk];              // 32 KiB
     __shared__ __attribute__((aligned(16))) double s12[kCubeIB][kWaves * kCubeRPW];   // 2 KiB
 
@@ -241,10 +362,8 @@ __global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) 
     const int rem = (int)(blockIdx.x % per_scene);
     const int jb = rem % args.j_blocks;
     const int ib = rem / args.j_blocks;
-    const int64_t c0 = args.cam_offs[3 * (int64_t)s];
-    const int N = (int)(args.cam_offs[3 * (int64_t)s + 1] - c0);
-    const int M = (int)(args.cam_offs[3 * (int64_t)s + 2] - args.cam_offs[3 * (int64_t)s + 1]);
-    const int P = (int)(args.cam_offs[3 * (int64_t)s + 3] - args.cam_offs[3 * (int64_t)s + 2]);
+    const Scene sc = scene_of(args.cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     const int jw0 = jb * kWaves * kCubeRPW;            // first j of the workgroup
     const int i0 = ib * kCubeIB;
     if (jw0 >= M || i0 >= N) return;                   // uniform over the workgroup
@@ -295,11 +414,7 @@ __global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) 
     for (int ii = 0; ii < ni; ++ii) {
         const int i = i0 + ii;
         double a13[kColsPerLane];
-        {
-            const f64x2 lo = *reinterpret_cast<const f64x2 *>(&s13[ii][kb]);
-            const f64x2 hi = *reinterpret_cast<const f64x2 *>(&s13[ii][kb + 2]);
-            a13[0] = lo.x; a13[1] = lo.y; a13[2] = hi.x; a13[3] = hi.y;
-        }
+        load4_lds(&s13[ii][kb], a13);
         uint32_t key[kCubeRPW];
         int32_t idx[kCubeRPW];
 #pragma unroll
@@ -307,15 +422,9 @@ __global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) 
             key[r] = kKeyInvalid;
             idx[r] = 0x7FFFFFFF;
             if (r >= nrows) continue;   // uniform
-            const double v12 = s12[ii][wave * kCubeRPW + r];
             double sum[kColsPerLane], q0[kColsPerLane];
-            bool ok = true;
-#pragma unroll
-            for (int q = 0; q < kColsPerLane; ++q) {
-                sum[q] = (v12 + a13[q]) + a23[r][q];          // (e12 + e13) + e23, :81
-                q0[q] = third_q(sum[q]);
-                ok &= third_ok(q0[q]);
-            }
+            const bool ok =
+                row_thirds<kColsPerLane, false>(s12[ii][wave * kCubeRPW + r], a13, a23[r], sum, q0);
             float v[kColsPerLane];
             const int64_t row = (int64_t)i * M + j0 + r;
             if (full && __all(ok || !act)) {
@@ -332,18 +441,9 @@ __global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) 
                 idx[r] = act ? b.j : 0x7FFFFFFF;
             } else {
                 Best b{__uint_as_float(0x7F800000u), 0x7FFFFFFF};
-                // the IEEE division only when some lane needs it (uniform branch)
-                double qq[kColsPerLane];
-#pragma unroll
-                for (int q = 0; q < kColsPerLane; ++q) qq[q] = q0[q];
-                if (!__all(ok || !act)) {
-#pragma unroll
-                    for (int q = 0; q < kColsPerLane; ++q)
-                        qq[q] = third_ok(q0[q]) ? q0[q] : sum[q] / 3.0;
-                }
+                row_exact(sum, q0, !__all(ok || !act), v);
 #pragma unroll
                 for (int q = 0; q < kColsPerLane; ++q) {
-                    v[q] = (float)qq[q];
                     if (q < kvalid) {
                         if (args.cube)
                             args.cube[coff + row * P + kb + q] = v[q];   // L2 merges the 4 strided dword stores
@@ -374,15 +474,7 @@ __global__ __launch_bounds__(kThreads) void triplet_tile_kernel(Cube3Args args) 
 // lane's 4 k into registers, e13 [IB][P] and e12 [IB][4*RPW] into LDS -- so
 // the cube costs one launch and no workspace write + read (the
 // workspace was ~10% of the cube's HBM traffic at 256^3).
-struct CubeFusedArgs {
-    const double *pts;
-    const int64_t *cam_offs;
-    const double *F;            // [S*3, 9]: F12, F13, F23
-    const int64_t *cube_offs;
-    const int64_t *row_offs;
-    float *cube;
-    int32_t *argmin;
-    float *minval;
+struct CubeFusedArgs : CubeIn, CubeOut {
     int32_t j_blocks, i_blocks;
     // optional (BM8 instantiations): per (scene, i, group of 8 j rows) the
     // minimum over the group of every k, as the upper 16 bits of its
@@ -428,23 +520,6 @@ __device__ __forceinline__ void bm8_store(uint16_t *row, int kb, int kvalid, con
         for (int q = 0; q < KPL; ++q)
             if (q < kvalid) row[kb + q] = (uint16_t)(k[q] >> 16);
     }
-}
-
-struct LineRec {
-    double l0, l1, l2;
-    double deg;                 // 1.0: degenerate line (9999 sentinel)
-};
-
-__device__ __forceinline__ double pair_e(const LineRec &col, const LineRec &row, double rx,
-                                         double ry, double cx, double cy) {
-    const double d1 = col.deg != 0.0 ? kSentinel : line_dist(col.l0, col.l1, col.l2, rx, ry);
-    const double d2 = row.deg != 0.0 ? kSentinel : line_dist(row.l0, row.l1, row.l2, cx, cy);
-    return 0.5 * (d1 + d2);                                                       // :28
-}
-
-__device__ __forceinline__ void load_f(const double *F, double f[9]) {
-#pragma unroll
-    for (int q = 0; q < 9; ++q) f[q] = F[q];
 }
 
 // SPLIT 2 / 4 (views of <= 128 / <= 64 detections, kCubeRPW == 8): the wave
@@ -511,19 +586,14 @@ void triplet_fused_kernel(CubeFusedArgs args) {
     // step ii the scene's tiles write the ADJACENT rows ii * IB' .. ii * IB' +
     // IB' - 1 -- one contiguous band of the cube per XCD, moving through it as
     // ii advances, instead of 16 bands 16 rows apart.
-    uint32_t blk = blockIdx.x;
-    {
-        const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blk % 8;
-        blk = x * q + min(x, r) + blk / 8;
-    }
+    const uint32_t blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
     const uint32_t per_scene = (uint32_t)(args.j_blocks * args.i_blocks);
     const int s = (int)(blk / per_scene);
     const int rem = (int)(blk % per_scene);
     const int jb = rem % args.j_blocks;
     const int ib = rem / args.j_blocks;
-    const int64_t *co = args.cam_offs + 3 * (int64_t)s;
-    const int64_t c0 = co[0], c1 = co[1], c2 = co[2];
-    const int N = (int)(c1 - c0), M = (int)(c2 - c1), P = (int)(co[3] - c2);
+    const Scene sc = scene_of(args.cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     const int jw0 = jb * kJ;
     // tile rows: ib + i_stride * ii, over THIS scene's i tiles: a view of
     // N < max_n rows fills ceil(N / IB) tiles (the rest exit) instead of
@@ -560,9 +630,7 @@ void triplet_fused_kernel(CubeFusedArgs args) {
     // which stores its remaining k alone
     const bool full = args.cube != nullptr;
     const bool act_k = kvalid > 0;
-    const double *F12 = args.F + (3 * (int64_t)s + 0) * 9;
-    const double *F13 = args.F + (3 * (int64_t)s + 1) * 9;
-    const double *F23 = args.F + (3 * (int64_t)s + 2) * 9;
+    const double *F12 = scene_F(args.F, s, 0), *F13 = scene_F(args.F, s, 1), *F23 = scene_F(args.F, s, 2);
 
     // ---- prologue 1: the tile's view-0 rows, view-1 rows/columns, and the
     // k columns' lines (one column per thread: kThreads == kChunk).  The F23
@@ -577,59 +645,27 @@ void triplet_fused_kernel(CubeFusedArgs args) {
     ColRec *s_c23 = reinterpret_cast<ColRec *>(&s13[0][0]);
     bool any_deg = false;   // a degenerate line among this thread's (9999 sentinel)
     if (t < kCubeIB) {
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (t < ni) {
-            double f[9];
-            px = args.pts[2 * (c0 + ib + i_stride * t)];
-            py = args.pts[2 * (c0 + ib + i_stride * t) + 1];
-            load_f(F13, f);
-            a.deg = row_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F12, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        any_deg |= (a.deg != 0.0) || (b.deg != 0.0);
-        s_r13[t] = a;
-        s_r12[t] = b;
-        s_p0[t][0] = px;
-        s_p0[t][1] = py;
+        const LinePair p = line_pair<true, true>(args.pts, sc.c0 + ib + i_stride * t, t < ni, F13, F12);
+        any_deg |= p.deg();
+        s_r13[t] = p.a;
+        s_r12[t] = p.b;
+        s_p0[t][0] = p.x;
+        s_p0[t][1] = p.y;
     } else if (t >= kWave && t < kWave + kJ) {
         const int jj = t - kWave;
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (jw0 + jj < M) {
-            double f[9];
-            px = args.pts[2 * (c1 + jw0 + jj)];
-            py = args.pts[2 * (c1 + jw0 + jj) + 1];
-            load_f(F12, f);
-            a.deg = col_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F23, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        any_deg |= (a.deg != 0.0) || (b.deg != 0.0);
-        s_c12[jj] = a;
-        s_r23[jj] = b;
-        s_p1[jj][0] = px;
-        s_p1[jj][1] = py;
+        const LinePair p = line_pair<false, true>(args.pts, sc.c1 + jw0 + jj, jw0 + jj < M, F12, F23);
+        any_deg |= p.deg();
+        s_c12[jj] = p.a;
+        s_r23[jj] = p.b;
+        s_p1[jj][0] = p.x;
+        s_p1[jj][1] = p.y;
     }
-    LineRec cl13{0.0, 0.0, 0.0, 0.0};   // column k = t, F13 (registers, for e13)
-    double kx = 0.0, ky = 0.0;
-    {
-        ColRec c23{{0.0, 0.0, 0.0, 0.0}, 0.0, 0.0};
-        if (t < P) {
-            double f[9];
-            kx = args.pts[2 * (c2 + t)];
-            ky = args.pts[2 * (c2 + t) + 1];
-            load_f(F13, f);
-            cl13.deg = col_line(f, kx, ky, cl13.l0, cl13.l1, cl13.l2) ? 1.0 : 0.0;
-            load_f(F23, f);
-            c23.l.deg = col_line(f, kx, ky, c23.l.l0, c23.l.l1, c23.l.l2) ? 1.0 : 0.0;
-            c23.x = kx;
-            c23.y = ky;
-            any_deg |= (cl13.deg != 0.0) || (c23.l.deg != 0.0);
-        }
-        if (t < kW13) s_c23[t] = c23;
-    }
+    // column k = t: its F13 line and point stay in registers (for e13)
+    const LinePair pk = line_pair<false, false>(args.pts, sc.c2 + t, t < P, F13, F23);
+    const LineRec cl13 = pk.a;
+    const double kx = pk.x, ky = pk.y;
+    if (t < P) any_deg |= pk.deg();
+    if (t < kW13) s_c23[t] = ColRec{pk.b, kx, ky};
     // uniform: no line of the tile is degenerate, so every residual is
     // 0.5 * (|l1 . p1| + |l2 . p2|) without the sentinel selects
     const bool no_deg = __syncthreads_and(!any_deg) != 0;
@@ -668,14 +704,7 @@ void triplet_fused_kernel(CubeFusedArgs args) {
     } else if (t < kW13) {
         for (int r = 0; r < kCubeIB; ++r) s13[r][t] = 0.0;
     }
-    for (int x = t; x < kCubeIB * kJ; x += kThreads) {
-        const int r = x / kJ, jj = x % kJ;
-        const double e = (r < ni && jw0 + jj < M)
-                             ? pair(s_c12[jj], s_r12[r], s_p0[r][0], s_p0[r][1], s_p1[jj][0], s_p1[jj][1])
-                             : 0.0;
-        s12[r][jj] = e;
-        tame_in &= e <= kTameResidual;
-    }
+    tame_in &= fill_e12(s12, s_c12, s_r12, s_p0, s_p1, ni, jw0, M, pair);
     // every sum of the tile is finite when its three residuals are <= 2^1020
     // (NaN fails the compare): then third_q is RN(s/3) for all of them and the
     // main loop needs no per-row check (a loop without the fallback path)
@@ -698,9 +727,7 @@ void triplet_fused_kernel(CubeFusedArgs args) {
             const uint64_t row_i = cube_base + (uint64_t)((int64_t)i * M + j0) * (uint64_t)P * 4u;
             double a13[KPL];
             if constexpr (KPL >= 4) {   // 4 k at kb (16-byte aligned), then panel 2's
-                const f64x2 lo = *reinterpret_cast<const f64x2 *>(&s13[ii][kb]);
-                const f64x2 hi = *reinterpret_cast<const f64x2 *>(&s13[ii][kb + 2]);
-                a13[0] = lo.x; a13[1] = lo.y; a13[2] = hi.x; a13[3] = hi.y;
+                load4_lds(&s13[ii][kb], a13);
 #pragma unroll
                 for (int q = 4; q < KPL; ++q) a13[q] = s13[ii][min(kpos(q), kW13 - 1)];
             } else {
@@ -719,15 +746,8 @@ void triplet_fused_kernel(CubeFusedArgs args) {
                 if (r >= nrows) continue;   // uniform (the lower half's row is the smaller)
                 const int rr = r + hl * kLaneRows;                 // the wave row
                 const bool act = act_k && rr < nrows;              // HALF: the upper row may not exist
-                const double v12 = s12[ii][wave * kCubeRPW + rr];
                 double sum[KPL], q0[KPL];
-                bool ok = true;
-#pragma unroll
-                for (int q = 0; q < KPL; ++q) {
-                    sum[q] = (v12 + a13[q]) + a23[r][q];          // (e12 + e13) + e23, :81
-                    q0[q] = third_q(sum[q]);
-                    if (!FAST) ok &= third_ok(q0[q]);
-                }
+                const bool ok = row_thirds<KPL, FAST>(s12[ii][wave * kCubeRPW + rr], a13, a23[r], sum, q0);
                 float v[KPL];
                 const int64_t row = (int64_t)i * M + j0 + rr;
                 if (FAST || (full && __all(ok || !act))) {
@@ -783,7 +803,10 @@ void triplet_fused_kernel(CubeFusedArgs args) {
                     idx[r] = act ? b.j : 0x7FFFFFFF;
                 } else {
                     Best b{__uint_as_float(0x7F800000u), 0x7FFFFFFF};
-                    // the IEEE division only when some lane needs it (uniform branch)
+                    // row_exact's arithmetic, written out: through the helper
+                    // the register allocation of the forms with the 8-row
+                    // minima moved (3 to 8 of them, by up to 6 VGPRs; DESIGN
+                    // §12.8), and their shapes are measured decisions
                     double qq[KPL];
 #pragma unroll
                     for (int q = 0; q < KPL; ++q) qq[q] = q0[q];
@@ -892,11 +915,7 @@ void triplet_fused_kernel(CubeFusedArgs args) {
         const uint64_t i_step = (uint64_t)i_stride * M * kRowBytes;
         for (int ii = 0; ii < ni; ++ii) {
             double a13[kColsPerLane];
-            {
-                const f64x2 lo = *reinterpret_cast<const f64x2 *>(&s13[ii][kb]);
-                const f64x2 hi = *reinterpret_cast<const f64x2 *>(&s13[ii][kb + 2]);
-                a13[0] = lo.x; a13[1] = lo.y; a13[2] = hi.x; a13[3] = hi.y;
-            }
+            load4_lds(&s13[ii][kb], a13);
             double v12s[kCubeRPW];   // the 8 rows' e12, read together (4 x 16 B)
 #pragma unroll
             for (int r = 0; r < kCubeRPW; r += 2) {
@@ -994,9 +1013,8 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
     const int rem = (int)(blk % per_scene);
     const int jb = rem % args.j_blocks;
     const int ib = rem / args.j_blocks;
-    const int64_t *co = args.cam_offs + 3 * (int64_t)s;
-    const int64_t c0 = co[0], c1 = co[1], c2 = co[2];
-    const int N = (int)(c1 - c0), M = (int)(c2 - c1), P = (int)(co[3] - c2);
+    const Scene sc = scene_of(args.cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     const int jw0 = jb * kJ;
     const int i0 = ib * kCubeIB;
     if (jw0 >= M || i0 >= N) return;                   // uniform over the workgroup
@@ -1010,55 +1028,26 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
     const int kb = kColsPerLane * lane;
     const int64_t coff = args.cube_offs[s];
     const int64_t roff = args.row_offs[s];
-    const double *F12 = args.F + (3 * (int64_t)s + 0) * 9;
-    const double *F13 = args.F + (3 * (int64_t)s + 1) * 9;
-    const double *F23 = args.F + (3 * (int64_t)s + 2) * 9;
+    const double *F12 = scene_F(args.F, s, 0), *F13 = scene_F(args.F, s, 1), *F23 = scene_F(args.F, s, 2);
 
     // ---- once per tile: view-0 rows, view-1 rows/columns, e12 ---------------
     if (t < kCubeIB) {
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (t < ni) {
-            double f[9];
-            px = args.pts[2 * (c0 + i0 + t)];
-            py = args.pts[2 * (c0 + i0 + t) + 1];
-            load_f(F13, f);
-            a.deg = row_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F12, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        s_r13[t] = a;
-        s_r12[t] = b;
-        s_p0[t][0] = px;
-        s_p0[t][1] = py;
+        const LinePair p = line_pair<true, true>(args.pts, sc.c0 + i0 + t, t < ni, F13, F12);
+        s_r13[t] = p.a;
+        s_r12[t] = p.b;
+        s_p0[t][0] = p.x;
+        s_p0[t][1] = p.y;
     } else if (t >= kWave && t < kWave + kJ) {
         const int jj = t - kWave;
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (jw0 + jj < M) {
-            double f[9];
-            px = args.pts[2 * (c1 + jw0 + jj)];
-            py = args.pts[2 * (c1 + jw0 + jj) + 1];
-            load_f(F12, f);
-            a.deg = col_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F23, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        s_c12[jj] = a;
-        s_r23[jj] = b;
-        s_p1[jj][0] = px;
-        s_p1[jj][1] = py;
+        const LinePair p = line_pair<false, true>(args.pts, sc.c1 + jw0 + jj, jw0 + jj < M, F12, F23);
+        s_c12[jj] = p.a;
+        s_r23[jj] = p.b;
+        s_p1[jj][0] = p.x;
+        s_p1[jj][1] = p.y;
     }
     __syncthreads();
-    bool tame12 = true;   // as triplet_fused_kernel's tame_in, for this thread's e12
-    for (int x = t; x < kCubeIB * kJ; x += kThreads) {
-        const int r = x / kJ, jj = x % kJ;
-        const double e = (r < ni && jw0 + jj < M)
-                             ? pair_e(s_c12[jj], s_r12[r], s_p0[r][0], s_p0[r][1], s_p1[jj][0], s_p1[jj][1])
-                             : 0.0;
-        s12[r][jj] = e;
-        tame12 &= e <= kTameResidual;
-    }
+    // as triplet_fused_kernel's tame_in, for this thread's e12
+    const bool tame12 = fill_e12(s12, s_c12, s_r12, s_p0, s_p1, ni, jw0, M, pair_e);
     uint32_t run_k[kSlots];
     int32_t run_i[kSlots];
 #pragma unroll
@@ -1072,7 +1061,7 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
         const int kvalid = Pc - kb;
         // the chunk's column points from a uniform base and 32-bit lane
         // offsets (saddr loads): no 64-bit per-lane address to keep
-        const double *pk = args.pts + 2 * (c2 + kc);
+        const double *pk = args.pts + 2 * (sc.c2 + kc);
         if (kc > 0) __syncthreads();   // every wave is done with the previous chunk's s13
         bool tame_in = tame12;
         {   // e13 of this chunk: one column per thread
@@ -1081,8 +1070,7 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
             load_f(F13, f13);
             if (k < Pc) {
                 const double x = pk[2 * k], y = pk[2 * k + 1];
-                LineRec cl{0.0, 0.0, 0.0, 0.0};
-                cl.deg = col_line(f13, x, y, cl.l0, cl.l1, cl.l2) ? 1.0 : 0.0;
+                const LineRec cl = line_rec<false>(f13, x, y);
 #pragma unroll 4
                 for (int r = 0; r < kCubeIB; ++r) {
                     const double e = r < ni ? pair_e(cl, s_r13[r], s_p0[r][0], s_p0[r][1], x, y) : 0.0;
@@ -1103,7 +1091,7 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
             if (q < kvalid) {
                 x = pk[2 * (kb + q)];
                 y = pk[2 * (kb + q) + 1];
-                cl.deg = col_line(f23, x, y, cl.l0, cl.l1, cl.l2) ? 1.0 : 0.0;
+                cl = line_rec<false>(f23, x, y);
             }
 #pragma unroll
             for (int r = 0; r < kCubeRPW; ++r) {
@@ -1120,16 +1108,23 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
         if (nrows <= 0) continue;   // uniform; the barriers above are still reached
 
         const bool act = kvalid > 0;
+        // row x = ii * RPW + r of the wave (lane x % 64, slot x / 64; x uniform):
+        // its lane keeps the chunk's minimum if strictly smaller
+        auto keep_min = [&](int x, bool mine, uint32_t km, int32_t im) {
+#pragma unroll
+            for (int z = 0; z < kSlots; ++z) {
+                if (z != x / kWave) continue;   // uniform
+                const bool take = mine && km < run_k[z];
+                run_k[z] = take ? km : run_k[z];
+                run_i[z] = take ? kc + im : run_i[z];
+            }
+        };
         auto chunk_loop = [&](auto fast_tag) {
             constexpr bool FAST = decltype(fast_tag)::value;
             for (int ii = 0; ii < ni; ++ii) {
                 const int i = i0 + ii;
                 double a13[kColsPerLane];
-                {
-                    const f64x2 lo = *reinterpret_cast<const f64x2 *>(&s13[ii][kb]);
-                    const f64x2 hi = *reinterpret_cast<const f64x2 *>(&s13[ii][kb + 2]);
-                    a13[0] = lo.x; a13[1] = lo.y; a13[2] = hi.x; a13[3] = hi.y;
-                }
+                load4_lds(&s13[ii][kb], a13);
                 uint32_t key[kCubeRPW];
                 int32_t idx[kCubeRPW];
 #pragma unroll
@@ -1137,15 +1132,9 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
                     key[r] = kKeyInvalid;
                     idx[r] = 0x7FFFFFFF;
                     if (r >= nrows) continue;   // uniform
-                    const double v12 = s12[ii][wave * kCubeRPW + r];
                     double sum[kColsPerLane], q0[kColsPerLane];
-                    bool ok = true;
-#pragma unroll
-                    for (int q = 0; q < kColsPerLane; ++q) {
-                        sum[q] = (v12 + a13[q]) + a23[r][q];          // (e12 + e13) + e23, :81
-                        q0[q] = third_q(sum[q]);
-                        if (!FAST) ok &= third_ok(q0[q]);
-                    }
+                    const bool ok =
+                        row_thirds<kColsPerLane, FAST>(s12[ii][wave * kCubeRPW + r], a13, a23[r], sum, q0);
                     float v[kColsPerLane];
                     const int64_t row = (int64_t)i * M + j0 + r;
                     if (FAST || (full && __all(ok || !act))) {
@@ -1170,18 +1159,9 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
                         idx[r] = act ? b.j : 0x7FFFFFFF;
                     } else {
                         Best b{__uint_as_float(0x7F800000u), 0x7FFFFFFF};
-                        // the IEEE division only when some lane needs it (uniform branch)
-                        double qq[kColsPerLane];
-#pragma unroll
-                        for (int q = 0; q < kColsPerLane; ++q) qq[q] = q0[q];
-                        if (!__all(ok || !act)) {
-#pragma unroll
-                            for (int q = 0; q < kColsPerLane; ++q)
-                                qq[q] = third_ok(q0[q]) ? q0[q] : sum[q] / 3.0;
-                        }
+                        row_exact(sum, q0, !__all(ok || !act), v);
 #pragma unroll
                         for (int q = 0; q < kColsPerLane; ++q) {
-                            v[q] = (float)qq[q];
                             if (q < kvalid) {
                                 if (args.cube)
                                     args.cube[coff + row * P + kc + kb + q] = v[q];
@@ -1203,14 +1183,7 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
                     uint32_t km;
                     int32_t im;
                     wave_argmin8_transposed(key, idx, lane, km, im, x0 % kWave);
-                    const bool mine = lane - x0 % kWave >= 0 && lane - x0 % kWave < nrows;
-#pragma unroll
-                    for (int z = 0; z < kSlots; ++z) {
-                        if (z != x0 / kWave) continue;   // uniform
-                        const bool take = mine && km < run_k[z];
-                        run_k[z] = take ? km : run_k[z];
-                        run_i[z] = take ? kc + im : run_i[z];
-                    }
+                    keep_min(x0, lane - x0 % kWave >= 0 && lane - x0 % kWave < nrows, km, im);
                     continue;
                 }
 #pragma unroll
@@ -1220,14 +1193,7 @@ __global__ __launch_bounds__(kThreads, 3) void triplet_fused_chunked_kernel(Cube
                     int32_t im;
                     wave_argmin(key[r], idx[r], km, im);
                     const int x = ii * kCubeRPW + r;   // uniform
-                    const bool mine = lane == (x % kWave);
-#pragma unroll
-                    for (int z = 0; z < kSlots; ++z) {
-                        if (z != x / kWave) continue;   // uniform
-                        const bool take = mine && km < run_k[z];
-                        run_k[z] = take ? km : run_k[z];
-                        run_i[z] = take ? kc + im : run_i[z];
-                    }
+                    keep_min(x, lane == (x % kWave), km, im);
                 }
             }
         };
@@ -1267,15 +1233,7 @@ constexpr int kSmallMaxN = 64;
 // 44 against the fused kernel of its time)
 constexpr int kSmallAutoMaxN = 16;
 
-struct CubeSmallArgs {
-    const double *pts;
-    const int64_t *cam_offs;
-    const double *F;            // [S*3, 9]: F12, F13, F23
-    const int64_t *cube_offs;
-    const int64_t *row_offs;
-    float *cube;
-    int32_t *argmin;
-    float *minval;
+struct CubeSmallArgs : CubeIn, CubeOut {
     int32_t max_n;
     int32_t ib;                 // rows i per workgroup
     int32_t i_blocks;           // ceil(max_n / ib)
@@ -1428,8 +1386,8 @@ __global__ __launch_bounds__(kThreads) void bmin8_from_cube_kernel(const int64_t
                                                                    int ir) {
     const int s = (int)(blockIdx.x / (unsigned)i_blocks);
     const int i0 = (int)(blockIdx.x % (unsigned)i_blocks) * ir;
-    const int64_t *co = cam_offs + 3 * (int64_t)s;
-    const int N = (int)(co[1] - co[0]), M = (int)(co[2] - co[1]), P = (int)(co[3] - co[2]);
+    const Scene sc = scene_of(cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     if (i0 >= N || M == 0 || P == 0) return;
     const int ni = min(ir, N - i0);
     const int g8 = (M + 7) / 8;
@@ -1520,10 +1478,7 @@ constexpr uint32_t kApproxMargin = 8;
 constexpr uint32_t kApproxTiny = 0x0D800000u;   // the bits of 2^-100
 constexpr float kThirdF = 1.0f / 3.0f;
 
-struct MinimaArgs {
-    const double *pts;
-    const int64_t *cam_offs;
-    const double *F;            // [S*3, 9]: F12, F13, F23
+struct MinimaArgs : CubeIn {
     uint16_t *bmin8;
     const int64_t *bmin8_offs;
     uint16_t *bm32;                 // 16-bit keys
@@ -1549,24 +1504,18 @@ __global__ __launch_bounds__(kThreads, 4) void triplet_minima_kernel(MinimaArgs 
     __shared__ __attribute__((aligned(16))) uint16_t s_bm[IB][kThreads];   // the chunk's block minima (16-bit)
 
     const int t = threadIdx.x;
-    uint32_t blk = blockIdx.x;   // each XCD a contiguous range of (scene, j block)s
-    {
-        const uint32_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = blk % 8;
-        blk = x * q + min(x, r) + blk / 8;
-    }
+    // each XCD a contiguous range of (scene, j block)s
+    const uint32_t blk = xcd_contiguous_block(blockIdx.x, gridDim.x);
     const int s = (int)(blk / (uint32_t)args.j_blocks);
     const int jb = (int)(blk % (uint32_t)args.j_blocks);
-    const int64_t *co = args.cam_offs + 3 * (int64_t)s;
-    const int64_t c0 = co[0], c1 = co[1], c2 = co[2];
-    const int N = (int)(c1 - c0), M = (int)(c2 - c1), P = (int)(co[3] - c2);
+    const Scene sc = scene_of(args.cam_offs, s);
+    const int N = sc.N, M = sc.M, P = sc.P;
     const int jw0 = jb * kJ;
     if (jw0 >= M || N == 0 || P == 0) return;   // uniform; an empty problem reads no cost
     const int nj = min(kJ, M - jw0);             // j rows of this block (uniform)
     const int k = t;
     const bool kv = k < P;
-    const double *F12 = args.F + (3 * (int64_t)s + 0) * 9;
-    const double *F13 = args.F + (3 * (int64_t)s + 1) * 9;
-    const double *F23 = args.F + (3 * (int64_t)s + 2) * 9;
+    const double *F12 = scene_F(args.F, s, 0), *F13 = scene_F(args.F, s, 1), *F23 = scene_F(args.F, s, 2);
     const int ld = args.ld;
     double *E12 = args.resid + (int64_t)s * args.stride;
     double *E13T = E12 + (int64_t)args.max_n * ld;
@@ -1580,54 +1529,26 @@ __global__ __launch_bounds__(kThreads, 4) void triplet_minima_kernel(MinimaArgs 
     // ---- once per workgroup: the block's j lines, this thread's k lines -----
     bool any_deg = false;
     if (t < kJ) {
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (t < nj) {
-            double f[9];
-            px = args.pts[2 * (c1 + jw0 + t)];
-            py = args.pts[2 * (c1 + jw0 + t) + 1];
-            load_f(F12, f);
-            a.deg = col_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F23, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        any_deg |= (a.deg != 0.0) || (b.deg != 0.0);
-        s_c12[t] = a;
-        s_r23[t] = b;
-        s_p1[t][0] = px;
-        s_p1[t][1] = py;
+        const LinePair p = line_pair<false, true>(args.pts, sc.c1 + jw0 + t, t < nj, F12, F23);
+        any_deg |= p.deg();
+        s_c12[t] = p.a;
+        s_r23[t] = p.b;
+        s_p1[t][0] = p.x;
+        s_p1[t][1] = p.y;
     }
-    LineRec cl13{0.0, 0.0, 0.0, 0.0}, c23{0.0, 0.0, 0.0, 0.0};
-    double kx = 0.0, ky = 0.0;
-    if (kv) {
-        double f[9];
-        kx = args.pts[2 * (c2 + k)];
-        ky = args.pts[2 * (c2 + k) + 1];
-        load_f(F13, f);
-        cl13.deg = col_line(f, kx, ky, cl13.l0, cl13.l1, cl13.l2) ? 1.0 : 0.0;
-        load_f(F23, f);
-        c23.deg = col_line(f, kx, ky, c23.l0, c23.l1, c23.l2) ? 1.0 : 0.0;
-        any_deg |= (cl13.deg != 0.0) || (c23.deg != 0.0);
-    }
+    const LinePair pk = line_pair<false, false>(args.pts, sc.c2 + k, kv, F13, F23);
+    const LineRec cl13 = pk.a, c23 = pk.b;
+    const double kx = pk.x, ky = pk.y;
+    if (kv) any_deg |= pk.deg();
     {   // row i = t's lines; a chunk (16 rows of one wave) is degenerate when
         // any of its rows is
-        LineRec a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
-        double px = 0.0, py = 0.0;
-        if (t < N) {
-            double f[9];
-            px = args.pts[2 * (c0 + t)];
-            py = args.pts[2 * (c0 + t) + 1];
-            load_f(F13, f);
-            a.deg = row_line(f, px, py, a.l0, a.l1, a.l2) ? 1.0 : 0.0;
-            load_f(F12, f);
-            b.deg = row_line(f, px, py, b.l0, b.l1, b.l2) ? 1.0 : 0.0;
-        }
-        s_r13[t] = a;
-        s_r12[t] = b;
-        s_p0[t][0] = px;
-        s_p0[t][1] = py;
+        const LinePair p = line_pair<true, true>(args.pts, sc.c0 + t, t < N, F13, F12);
+        s_r13[t] = p.a;
+        s_r12[t] = p.b;
+        s_p0[t][0] = p.x;
+        s_p0[t][1] = p.y;
         static_assert(kWave % IB == 0, "a wave's rows: whole chunks");
-        const uint64_t dm = __ballot((a.deg != 0.0) || (b.deg != 0.0));
+        const uint64_t dm = __ballot(p.deg());
         if (t % kWave < kWave / IB)
             s_degc[t / kWave * (kWave / IB) + t % kWave] = ((dm >> (IB * (t % kWave))) & ((1ull << IB) - 1)) != 0;
     }
@@ -1859,12 +1780,7 @@ __global__ __launch_bounds__(kThreads, 4) void triplet_minima_kernel(MinimaArgs 
     }
 }
 
-int cube_launch(const double *pts_dev, const int64_t *cam_offs_dev, const double *F_dev,
-                int32_t n_scenes, int32_t max_n, const int64_t *cube_offs_dev,
-                const int64_t *row_offs_dev, float *cube_dev, int32_t *argmin_dev, float *minval_dev,
-                uint16_t *bmin8_dev, const int64_t *bmin8_offs_dev, void *workspace_dev,
-                size_t workspace_bytes, const mvm_options *opts, hipStream_t s, bool &emitted);
-
+// ================================================================= host ====
 int grid_check(int64_t blocks) {
     if (blocks > kMaxGridBlocks)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "grid of %lld workgroups too large: split the scenes",
@@ -1872,21 +1788,234 @@ int grid_check(int64_t blocks) {
     return MVM_OK;
 }
 
-CubeFusedArgs fused_args(const double *pts, const int64_t *cam_offs, const double *F,
-                         const int64_t *cube_offs, const int64_t *row_offs, float *cube,
-                         int32_t *argmin, float *minval, int max_n, int ib, int rpw = 8) {
-    CubeFusedArgs c{};
-    c.pts = pts;
-    c.cam_offs = cam_offs;
-    c.F = F;
-    c.cube_offs = cube_offs;
-    c.row_offs = row_offs;
-    c.cube = cube;
-    c.argmin = argmin;
-    c.minval = minval;
+// the fused grid: tiles of ib i rows x 4 waves of rpw j rows
+CubeFusedArgs fused_args(const CubeIn &in, const CubeOut &out, int max_n, int ib, int rpw = 8) {
+    CubeFusedArgs c{in, out};
     c.j_blocks = (max_n + kWaves * rpw - 1) / (kWaves * rpw);
     c.i_blocks = (max_n + ib - 1) / ib;
     return c;
+}
+
+// The fused kernel's form for a batch whose largest view holds max_n detections
+struct LaneShape {
+    int split;       // (i, j) rows per wave instruction: 1, 2, 4 or 8
+    int kpl;         // k per lane: 3-8
+    bool j48;        // tiles of 48 j (12 rows per wave)
+    int tile_rows;   // i rows per tile: 16 or 32
+    bool bm8;        // the kernel writes the 8-row minima itself
+};
+
+// Tiles of 16 (32) i x 32 j; views of <= 32 / <= 64 / <= 128 put eight / four
+// / two (i, j) rows in every wave instruction; 3 k per lane where the view
+// fits them (<= 24 / 48 / 96 / 192 at eight / four / two / one rows per
+// instruction).  MVM_OK and the shape, or the error of an option the view
+// does not fit.  Views of more than 256 (the k-chunked kernel) take one row
+// per instruction and 4 k per lane.
+int cube_lane_shape(int max_n, const mvm_options &o, bool wants_bmin8, LaneShape &sh) {
+    const int want = o.cube_rows_per_instr ? o.cube_rows_per_instr : 8;
+    int split = (want >= 8 && max_n <= 4 * (kWave / 8)) ? 8
+              : (want >= 4 && max_n <= kChunk / 4) ? 4 : (want >= 2 && max_n <= kChunk / 2) ? 2 : 1;
+    if (o.cube_cols_per_lane == 3) {
+        // 3 k per lane forced: fewer rows per instruction until a row's
+        // 64 / split lanes hold the view (unless those are forced too);
+        // views of more than 256 run the k-chunked kernel, 4 k per lane only
+        if (max_n > kChunk)
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane 3: views of %d detections "
+                            "take the k-chunked kernel (4 k per lane)", (int)max_n);
+        while (split > 1 && max_n > 3 * (kWave / split) && !o.cube_rows_per_instr) split /= 2;
+        if (max_n > 3 * (kWave / split))
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT,
+                            "cube_cols_per_lane 3: views of %d detections exceed %d k per row",
+                            (int)max_n, 3 * (kWave / split));
+    }
+    int kpl = o.cube_cols_per_lane ? o.cube_cols_per_lane : (max_n <= 3 * (kWave / split) ? 3 : 4);
+    if (o.cube_cols_per_lane >= 5) {
+        // 5-8 k per lane forced: the split forms only (2 or 4 rows per
+        // instruction), the most rows per instruction whose lanes hold the view
+        if (max_n > kChunk)
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d: views of %d detections "
+                            "take the k-chunked kernel (4 k per lane)", kpl, (int)max_n);
+        split = 0;
+        for (int sp = 4; sp >= 2 && !split; sp /= 2)
+            if ((!o.cube_rows_per_instr || o.cube_rows_per_instr == sp) && (kWave / sp) * kpl >= max_n)
+                split = sp;
+        if (!split)
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d: no 2 or 4 rows per "
+                            "instruction hold views of %d detections", kpl, (int)max_n);
+    } else if (!o.cube_cols_per_lane && !o.cube_rows_per_instr && max_n <= kChunk) {
+        // a split form with 5-8 k per lane when it keeps >= 8 % more of the
+        // lanes busy than the 3 / 4 k shape (e.g. 130: 2 rows x 5 k, 81%,
+        // against 1 row x 3 k, 68%; 100: 4 rows x 7 k, 89%, against 78%)
+        double best = (double)max_n / ((kWave / split) * kpl);
+        for (int sp = 4; sp >= 2; sp /= 2) {
+            const int lpr = kWave / sp, k = (max_n + lpr - 1) / lpr;
+            const double u = (double)max_n / (lpr * k);
+            if (k >= 5 && k <= 8 && u >= best + 0.08) {
+                best = u;
+                split = sp;
+                kpl = k;
+            }
+        }
+    }
+    // views of 33-48 at four rows per instruction and 3 k per lane: tiles
+    // of 48 j (12 rows per wave), so a view of 48 fills one tile instead of
+    // leaving half of a second 32-wide tile empty
+    // (not when the 8-row minima are wanted: the 8-row waves write them,
+    // the 12-row ones would leave them to a pass over the cube)
+    const bool j48 = split == 4 && kpl == 3 && max_n > kWaves * 8 && !wants_bmin8;
+    // i rows per tile: 32 on request in the split forms (ABI 6), and by
+    // default at eight rows per instruction (views of <= 32: a tile of
+    // 16 i rows of such a view is mostly prologue; 24^3 0.663 -> 0.571,
+    // 32^3 0.456 -> 0.426 ms per 2 GB launch)
+    const int tile_rows =
+        split > 1 && (o.cube_tile_rows == 32 || (o.cube_tile_rows == 0 && split == 8)) ? 32 : 16;
+    // the 8-row minima from the same kernel (not the k-chunked one), in the
+    // split forms but for the 48-j tiles (12 rows per wave) and only with
+    // tiles of 32 i rows at eight rows per instruction, 16 otherwise (the
+    // shapes the defaults take)
+    const bool bm8 = wants_bmin8 && max_n <= kChunk &&
+                     (split == 1 || (!j48 && tile_rows == (split == 8 ? 32 : 16)));
+    sh = LaneShape{split, kpl, j48, tile_rows, bm8};
+    return MVM_OK;
+}
+
+// The forms of triplet_fused_kernel<IB, 8 (12: j48), SPLIT, KPL, BM8> that
+// cube_lane_shape's shapes take -- 48 and the two 48-j ones; no other is built
+constexpr bool fused_form(int ib, int split, int kpl, bool bm8) {
+    if (split == 1 || split == 8) return kpl <= 4 && (split == 8 || ib == 16);
+    return !(bm8 && ib == 32);   // two / four rows: the 8-row minima with tiles of 16 only
+}
+
+// the one place that names triplet_fused_kernel<...>; false: no such form
+bool launch_fused(const LaneShape &sh, dim3 grid, hipStream_t s, const CubeFusedArgs &c) {
+    bool launched = false;
+    dispatch_bool(sh.tile_rows == 32, [&](auto ib32) {
+        dispatch_bool(sh.bm8, [&](auto bm8) {
+            dispatch_int<1, 2, 4, 8>(sh.split, [&](auto split) {
+                dispatch_int<3, 4, 5, 6, 7, 8>(sh.kpl, [&](auto kpl) {
+                    constexpr int IB = decltype(ib32)::value ? 32 : 16;
+                    constexpr int SPLIT = decltype(split)::value, KPL = decltype(kpl)::value;
+                    constexpr bool BM8 = decltype(bm8)::value;
+                    if constexpr (fused_form(IB, SPLIT, KPL, BM8)) {
+                        launched = true;
+                        if constexpr (SPLIT == 4 && KPL == 3 && !BM8) {
+                            if (sh.j48) {
+                                triplet_fused_kernel<IB, 12, 4, 3><<<grid, dim3(kThreads), 0, s>>>(c);
+                                return;
+                            }
+                        }
+                        triplet_fused_kernel<IB, 8, SPLIT, KPL, BM8><<<grid, dim3(kThreads), 0, s>>>(c);
+                    }
+                });
+            });
+        });
+    });
+    return launched;
+}
+
+// every cube path: checks, the small kernel, the fused forms, the workspace
+// forms; `emitted`: the launched kernel wrote bmin8 itself
+int cube_launch(const double *pts_dev, const int64_t *cam_offs_dev, const double *F_dev,
+                int32_t n_scenes, int32_t max_n, const int64_t *cube_offs_dev,
+                const int64_t *row_offs_dev, float *cube_dev, int32_t *argmin_dev, float *minval_dev,
+                uint16_t *bmin8_dev, const int64_t *bmin8_offs_dev, void *workspace_dev,
+                size_t workspace_bytes, const mvm_options *opts, hipStream_t s, bool &emitted) {
+    mvm_options o;
+    int st = mvm_resolve_options(opts, o);
+    if (st) return st;
+    if (n_scenes < 0 || max_n < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative sizes");
+    if (o.cube_kernel < MVM_CUBE_DEFAULT || o.cube_kernel > MVM_CUBE_GENERIC)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_kernel %d", (int)o.cube_kernel);
+    if (o.cube_rows_per_instr != 0 && o.cube_rows_per_instr != 1 && o.cube_rows_per_instr != 2 &&
+        o.cube_rows_per_instr != 4 && o.cube_rows_per_instr != 8)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_rows_per_instr %d not 0, 1, 2, 4 or 8",
+                        (int)o.cube_rows_per_instr);
+    if (o.cube_cols_per_lane != 0 && (o.cube_cols_per_lane < 3 || o.cube_cols_per_lane > 8))
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d not 0 or 3..8",
+                        (int)o.cube_cols_per_lane);
+    if (o.cube_tile_rows != 0 && o.cube_tile_rows != 16 && o.cube_tile_rows != 32)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_tile_rows %d not 0, 16 or 32", (int)o.cube_tile_rows);
+    if (n_scenes == 0 || max_n == 0) return MVM_OK;
+    if (!pts_dev || !cam_offs_dev || !F_dev || !row_offs_dev)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
+    if (cube_dev && !cube_offs_dev) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube without cube_offs");
+    const size_t need = mvm_triplet_workspace_bytes(n_scenes, max_n);
+    if (!workspace_dev || workspace_bytes < need)
+        return mvm_fail(MVM_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
+    if (((uintptr_t)workspace_dev & 15) != 0)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "workspace not 16-byte aligned");
+    const int kernel = o.cube_kernel;
+    const CubeIn in{pts_dev, cam_offs_dev, F_dev};
+    const CubeOut out{cube_offs_dev, row_offs_dev, cube_dev, argmin_dev, minval_dev};
+
+    // the one-workgroup-per-scene kernel: by default up to kSmallAutoMaxN
+    // (measured crossover vs the fused four-rows-per-wave form), on request
+    // up to its limit; everything in LDS, no workspace pass
+    const bool small = kernel == MVM_CUBE_DEFAULT ? max_n <= kSmallAutoMaxN
+                                                  : (kernel == MVM_CUBE_SMALL && max_n < kSmallMaxN);
+    if (small) {
+        CubeSmallArgs c{in, out};
+        c.max_n = max_n;
+        // rows i per workgroup: the whole scene up to 32 detections, then
+        // 16-row blocks
+        c.ib = max_n <= 32 ? max_n : 16;
+        c.i_blocks = (max_n + c.ib - 1) / c.ib;
+        const size_t lds = small_lds_bytes(max_n, c.ib);
+        if ((st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(&triplet_small_kernel), lds)))
+            return st;
+        const int64_t blocks = (int64_t)n_scenes * c.i_blocks;
+        if ((st = grid_check(blocks))) return st;
+        triplet_small_kernel<<<dim3((unsigned)blocks), dim3(kThreads), lds, s>>>(c);
+        return mvm_check_launch("triplet_small_kernel");
+    }
+    if (kernel == MVM_CUBE_DEFAULT || kernel == MVM_CUBE_SMALL || kernel == MVM_CUBE_FUSED) {
+        LaneShape sh;
+        if ((st = cube_lane_shape(max_n, o, bmin8_dev != nullptr, sh))) return st;
+        CubeFusedArgs c = fused_args(in, out, max_n, sh.tile_rows, sh.j48 ? 12 : 8);
+        c.bmin8 = bmin8_dev;
+        c.bmin8_offs = bmin8_offs_dev;
+        const int64_t blocks = (int64_t)n_scenes * c.j_blocks * c.i_blocks;
+        if ((st = grid_check(blocks))) return st;
+        const dim3 grid((unsigned)blocks);
+        if (max_n > kChunk) {
+            // views of more than 256: fused tiles walking k in chunks of 256
+            triplet_fused_chunked_kernel<16, 8><<<grid, dim3(kThreads), 0, s>>>(c);
+            return mvm_check_launch("triplet_fused_chunked_kernel");
+        }
+        if (!launch_fused(sh, grid, s, c))
+            return mvm_fail(MVM_ERR_UNSUPPORTED, "no fused kernel of %d rows per instruction, %d k per "
+                            "lane, tiles of %d", sh.split, sh.kpl, sh.tile_rows);
+        emitted = sh.bm8;
+        return mvm_check_launch("triplet_fused_kernel");
+    }
+    // workspace forms: the fp64 pair matrices e12, e13, e23 of every scene
+    // (pairs (0,1), (0,2), (1,2): F12, F13, F23, process_pose.py:157-159)
+    const int64_t ld = ((int64_t)max_n + 3) / 4 * 4;
+    const int64_t mat_stride = (int64_t)max_n * ld;
+    const int32_t pa[3] = {0, 0, 1}, pb[3] = {1, 2, 2};
+    st = mvm_pairwise_residual_f64(pts_dev, cam_offs_dev, F_dev, pa, pb, n_scenes, 3, 3, max_n,
+                                   mat_stride, ld, (double *)workspace_dev, reinterpret_cast<mvm_stream_t>(s));
+    if (st) return st;
+    CubeArgs c{out};
+    c.cam_offs = cam_offs_dev;
+    c.e = (const double *)workspace_dev;
+    c.mat_stride = mat_stride;
+    c.ld = ld;
+    if (kernel == MVM_CUBE_WORKSPACE && max_n <= kChunk) {
+        c.j_blocks = (max_n + kWaves * 8 - 1) / (kWaves * 8);
+        c.i_blocks = (max_n + 16 - 1) / 16;
+        const int64_t blocks = (int64_t)n_scenes * c.j_blocks * c.i_blocks;
+        if ((st = grid_check(blocks))) return st;
+        triplet_tile_kernel<16, 8><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(c);
+        return mvm_check_launch("triplet_tile_kernel");
+    }
+    const int rows_per_wg = kWaves * kTripletRowsPerWave;
+    c.j_blocks = (max_n + rows_per_wg - 1) / rows_per_wg;
+    c.i_blocks = max_n;
+    const int64_t blocks = (int64_t)n_scenes * max_n * c.j_blocks;
+    if ((st = grid_check(blocks))) return st;
+    triplet_kernel<kTripletRowsPerWave><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(c);
+    return mvm_check_launch("triplet_kernel");
 }
 
 }  // namespace
@@ -1962,10 +2091,7 @@ int mvm_triplet_minima(const double *pts_dev, const int64_t *cam_offs_dev, const
         return mvm_fail(MVM_ERR_WORKSPACE, "residual workspace %zu bytes < required %zu", resid_bytes, need);
     if (((uintptr_t)resid_dev & 15) != 0)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "residual workspace not 16-byte aligned");
-    MinimaArgs a{};
-    a.pts = pts_dev;
-    a.cam_offs = cam_offs_dev;
-    a.F = F_dev;
+    MinimaArgs a{CubeIn{pts_dev, cam_offs_dev, F_dev}};
     a.bmin8 = bmin8_dev;
     a.bmin8_offs = bmin8_offs_dev;
     a.bm32 = bm32_dev;
@@ -1986,257 +2112,14 @@ int mvm_triplet_minima(const double *pts_dev, const int64_t *cam_offs_dev, const
     return mvm_check_launch("triplet_minima_kernel");
 }
 
-}  // extern "C"
-
-namespace {
-
-// the fused kernel at two / four / eight rows per instruction, tiles of IB i
-// rows; BM8: it also writes the 8-row minima (not the 48-j tiles' 12-row waves)
-template <int IB, bool BM8 = false>
-void launch_split(int split, int kpl, bool j48, dim3 grid, dim3 block, hipStream_t s, const CubeFusedArgs &c) {
-    if (split == 8) {   // views of <= 32: eight rows per instruction
-        if (kpl == 3) triplet_fused_kernel<IB, 8, 8, 3, BM8><<<grid, block, 0, s>>>(c);
-        else triplet_fused_kernel<IB, 8, 8, 4, BM8><<<grid, block, 0, s>>>(c);
-        return;
-    }
-    if constexpr (BM8 && IB == 32) {   // not launched (the host's bm8 rule): not instantiated
-        return;
-    } else if (split == 4) {
-        if (j48 && !BM8) {
-            triplet_fused_kernel<IB, 12, 4, 3><<<grid, block, 0, s>>>(c);
-            return;
-        }
-        switch (kpl) {
-        case 3: triplet_fused_kernel<IB, 8, 4, 3, BM8><<<grid, block, 0, s>>>(c); break;
-        case 4: triplet_fused_kernel<IB, 8, 4, 4, BM8><<<grid, block, 0, s>>>(c); break;
-        case 5: triplet_fused_kernel<IB, 8, 4, 5, BM8><<<grid, block, 0, s>>>(c); break;
-        case 6: triplet_fused_kernel<IB, 8, 4, 6, BM8><<<grid, block, 0, s>>>(c); break;
-        case 7: triplet_fused_kernel<IB, 8, 4, 7, BM8><<<grid, block, 0, s>>>(c); break;
-        default: triplet_fused_kernel<IB, 8, 4, 8, BM8><<<grid, block, 0, s>>>(c); break;
-        }
-    } else {
-        switch (kpl) {
-        case 3: triplet_fused_kernel<IB, 8, 2, 3, BM8><<<grid, block, 0, s>>>(c); break;
-        case 4: triplet_fused_kernel<IB, 8, 2, 4, BM8><<<grid, block, 0, s>>>(c); break;
-        case 5: triplet_fused_kernel<IB, 8, 2, 5, BM8><<<grid, block, 0, s>>>(c); break;
-        case 6: triplet_fused_kernel<IB, 8, 2, 6, BM8><<<grid, block, 0, s>>>(c); break;
-        case 7: triplet_fused_kernel<IB, 8, 2, 7, BM8><<<grid, block, 0, s>>>(c); break;
-        default: triplet_fused_kernel<IB, 8, 2, 8, BM8><<<grid, block, 0, s>>>(c); break;
-        }
-    }
-}
-
-// every cube path; `emitted`: the launched kernel wrote bmin8 itself
-int cube_launch(const double *pts_dev, const int64_t *cam_offs_dev, const double *F_dev,
-                int32_t n_scenes, int32_t max_n, const int64_t *cube_offs_dev,
-                const int64_t *row_offs_dev, float *cube_dev, int32_t *argmin_dev, float *minval_dev,
-                uint16_t *bmin8_dev, const int64_t *bmin8_offs_dev, void *workspace_dev,
-                size_t workspace_bytes, const mvm_options *opts, hipStream_t s, bool &emitted) {
-    mvm_options o;
-    int st = mvm_resolve_options(opts, o);
-    if (st) return st;
-    if (n_scenes < 0 || max_n < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative sizes");
-    if (o.cube_kernel < MVM_CUBE_DEFAULT || o.cube_kernel > MVM_CUBE_GENERIC)
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_kernel %d", (int)o.cube_kernel);
-    if (o.cube_rows_per_instr != 0 && o.cube_rows_per_instr != 1 && o.cube_rows_per_instr != 2 &&
-        o.cube_rows_per_instr != 4 && o.cube_rows_per_instr != 8)
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_rows_per_instr %d not 0, 1, 2, 4 or 8",
-                        (int)o.cube_rows_per_instr);
-    if (o.cube_cols_per_lane != 0 && (o.cube_cols_per_lane < 3 || o.cube_cols_per_lane > 8))
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d not 0 or 3..8",
-                        (int)o.cube_cols_per_lane);
-    if (o.cube_tile_rows != 0 && o.cube_tile_rows != 16 && o.cube_tile_rows != 32)
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_tile_rows %d not 0, 16 or 32", (int)o.cube_tile_rows);
-    if (n_scenes == 0 || max_n == 0) return MVM_OK;
-    if (!pts_dev || !cam_offs_dev || !F_dev || !row_offs_dev)
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
-    if (cube_dev && !cube_offs_dev) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube without cube_offs");
-    const size_t need = mvm_triplet_workspace_bytes(n_scenes, max_n);
-    if (!workspace_dev || workspace_bytes < need)
-        return mvm_fail(MVM_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
-    if (((uintptr_t)workspace_dev & 15) != 0)
-        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "workspace not 16-byte aligned");
-    const int kernel = o.cube_kernel;
-
-    // the one-workgroup-per-scene kernel: by default up to kSmallAutoMaxN
-    // (measured crossover vs the fused four-rows-per-wave form), on request
-    // up to its limit; everything in LDS, no workspace pass
-    const bool small = kernel == MVM_CUBE_DEFAULT ? max_n <= kSmallAutoMaxN
-                                                  : (kernel == MVM_CUBE_SMALL && max_n < kSmallMaxN);
-    if (small) {
-        CubeSmallArgs c{};
-        c.pts = pts_dev;
-        c.cam_offs = cam_offs_dev;
-        c.F = F_dev;
-        c.cube_offs = cube_offs_dev;
-        c.row_offs = row_offs_dev;
-        c.cube = cube_dev;
-        c.argmin = argmin_dev;
-        c.minval = minval_dev;
-        c.max_n = max_n;
-        // rows i per workgroup: the whole scene up to 32 detections, then
-        // 16-row blocks (tools/gpu_cube_small.sh)
-        c.ib = max_n <= 32 ? max_n : 16;
-        c.i_blocks = (max_n + c.ib - 1) / c.ib;
-        const size_t lds = small_lds_bytes(max_n, c.ib);
-        if ((st = mvm_raise_dynamic_lds(reinterpret_cast<const void *>(&triplet_small_kernel), lds)))
-            return st;
-        const int64_t blocks = (int64_t)n_scenes * c.i_blocks;
-        if ((st = grid_check(blocks))) return st;
-        triplet_small_kernel<<<dim3((unsigned)blocks), dim3(kThreads), lds, s>>>(c);
-        return mvm_check_launch("triplet_small_kernel");
-    }
-    if (kernel == MVM_CUBE_DEFAULT || kernel == MVM_CUBE_SMALL || kernel == MVM_CUBE_FUSED) {
-        // tiles of 16 (32) i x 32 j; views of <= 32 / <= 64 / <= 128 put
-        // eight / four / two (i, j) rows in every wave instruction; 3 k per
-        // lane where the view fits them (<= 24 / 48 / 96 / 192 at eight / four
-        // / two / one rows per instruction)
-        const int want = o.cube_rows_per_instr ? o.cube_rows_per_instr : 8;
-        int split = (want >= 8 && max_n <= 4 * (kWave / 8)) ? 8
-                  : (want >= 4 && max_n <= kChunk / 4) ? 4 : (want >= 2 && max_n <= kChunk / 2) ? 2 : 1;
-        if (o.cube_cols_per_lane == 3) {
-            // 3 k per lane forced: fewer rows per instruction until a row's
-            // 64 / split lanes hold the view (unless those are forced too);
-            // views of more than 256 run the k-chunked kernel, 4 k per lane only
-            if (max_n > kChunk)
-                return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane 3: views of %d detections "
-                                "take the k-chunked kernel (4 k per lane)", (int)max_n);
-            while (split > 1 && max_n > 3 * (kWave / split) && !o.cube_rows_per_instr) split /= 2;
-            if (max_n > 3 * (kWave / split))
-                return mvm_fail(MVM_ERR_INVALID_ARGUMENT,
-                                "cube_cols_per_lane 3: views of %d detections exceed %d k per row",
-                                (int)max_n, 3 * (kWave / split));
-        }
-        int kpl = o.cube_cols_per_lane ? o.cube_cols_per_lane : (max_n <= 3 * (kWave / split) ? 3 : 4);
-        if (o.cube_cols_per_lane >= 5) {
-            // 5-8 k per lane forced: the split forms only (2 or 4 rows per
-            // instruction), the most rows per instruction whose lanes hold the view
-            if (max_n > kChunk)
-                return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d: views of %d detections "
-                                "take the k-chunked kernel (4 k per lane)", kpl, (int)max_n);
-            split = 0;
-            for (int sp = 4; sp >= 2 && !split; sp /= 2)
-                if ((!o.cube_rows_per_instr || o.cube_rows_per_instr == sp) && (kWave / sp) * kpl >= max_n)
-                    split = sp;
-            if (!split)
-                return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube_cols_per_lane %d: no 2 or 4 rows per "
-                                "instruction hold views of %d detections", kpl, (int)max_n);
-        } else if (!o.cube_cols_per_lane && !o.cube_rows_per_instr && max_n <= kChunk) {
-            // a split form with 5-8 k per lane when it keeps >= 8 % more of the
-            // lanes busy than the 3 / 4 k shape (e.g. 130: 2 rows x 5 k, 81%,
-            // against 1 row x 3 k, 68%; 100: 4 rows x 7 k, 89%, against 78%)
-            double best = (double)max_n / ((kWave / split) * kpl);
-            for (int sp = 4; sp >= 2; sp /= 2) {
-                const int lpr = kWave / sp, k = (max_n + lpr - 1) / lpr;
-                const double u = (double)max_n / (lpr * k);
-                if (k >= 5 && k <= 8 && u >= best + 0.08) {
-                    best = u;
-                    split = sp;
-                    kpl = k;
-                }
-            }
-        }
-        // views of 33-48 at four rows per instruction and 3 k per lane: tiles
-        // of 48 j (12 rows per wave), so a view of 48 fills one tile instead of
-        // leaving half of a second 32-wide tile empty
-        // (not when the 8-row minima are wanted: the 8-row waves write them,
-        // the 12-row ones would leave them to a pass over the cube)
-        const bool j48 = split == 4 && kpl == 3 && max_n > kWaves * 8 && !bmin8_dev;
-        // i rows per tile: 32 on request in the split forms (ABI 6), and by
-        // default at eight rows per instruction (views of <= 32: a tile of
-        // 16 i rows of such a view is mostly prologue; 24^3 0.663 -> 0.571,
-        // 32^3 0.456 -> 0.426 ms per 2 GB launch)
-        const int tile_rows =
-            split > 1 && (o.cube_tile_rows == 32 || (o.cube_tile_rows == 0 && split == 8)) ? 32 : 16;
-        CubeFusedArgs c = fused_args(pts_dev, cam_offs_dev, F_dev, cube_offs_dev, row_offs_dev,
-                                     cube_dev, argmin_dev, minval_dev, max_n, tile_rows, j48 ? 12 : 8);
-        c.bmin8 = bmin8_dev;
-        c.bmin8_offs = bmin8_offs_dev;
-        const int64_t blocks = (int64_t)n_scenes * c.j_blocks * c.i_blocks;
-        if ((st = grid_check(blocks))) return st;
-        const dim3 grid((unsigned)blocks), block(kThreads);
-        if (max_n > kChunk) {
-            // views of more than 256: fused tiles walking k in chunks of 256
-            triplet_fused_chunked_kernel<16, 8><<<grid, block, 0, s>>>(c);
-            return mvm_check_launch("triplet_fused_chunked_kernel");
-        }
-        if (split > 1) {
-            // the 8-row minima from the same kernel, but for the 48-j tiles
-            // (12 rows per wave); tiles of 32 i rows at eight rows per
-            // instruction, 16 otherwise (the shapes the defaults take)
-            const bool bm8 = bmin8_dev && !j48 && tile_rows == (split == 8 ? 32 : 16);
-            if (bm8) {
-                if (tile_rows == 32) launch_split<32, true>(split, kpl, j48, grid, block, s, c);
-                else launch_split<16, true>(split, kpl, j48, grid, block, s, c);
-                emitted = true;
-            } else if (tile_rows == 32) {
-                launch_split<32>(split, kpl, j48, grid, block, s, c);
-            } else {
-                launch_split<16>(split, kpl, j48, grid, block, s, c);
-            }
-        } else if (bmin8_dev) {                  // the 8-row minima from the same kernel
-            if (kpl == 3) triplet_fused_kernel<16, 8, 1, 3, true><<<grid, block, 0, s>>>(c);
-            else triplet_fused_kernel<16, 8, 1, kColsPerLane, true><<<grid, block, 0, s>>>(c);
-            emitted = true;
-        } else {
-            if (kpl == 3) triplet_fused_kernel<16, 8, 1, 3><<<grid, block, 0, s>>>(c);
-            else triplet_fused_kernel<16, 8><<<grid, block, 0, s>>>(c);
-        }
-        return mvm_check_launch("triplet_fused_kernel");
-    }
-    // workspace forms: the fp64 pair matrices e12, e13, e23 of every scene
-    // (pairs (0,1), (0,2), (1,2): F12, F13, F23, process_pose.py:157-159)
-    const int64_t ld = ((int64_t)max_n + 3) / 4 * 4;
-    const int64_t mat_stride = (int64_t)max_n * ld;
-    const int32_t pa[3] = {0, 0, 1}, pb[3] = {1, 2, 2};
-    st = mvm_pairwise_residual_f64(pts_dev, cam_offs_dev, F_dev, pa, pb, n_scenes, 3, 3, max_n,
-                                   mat_stride, ld, (double *)workspace_dev, reinterpret_cast<mvm_stream_t>(s));
-    if (st) return st;
-    if (kernel == MVM_CUBE_WORKSPACE && max_n <= kChunk) {
-        Cube3Args c{};
-        c.cam_offs = cam_offs_dev;
-        c.e = (const double *)workspace_dev;
-        c.mat_stride = mat_stride;
-        c.ld = ld;
-        c.cube_offs = cube_offs_dev;
-        c.row_offs = row_offs_dev;
-        c.cube = cube_dev;
-        c.argmin = argmin_dev;
-        c.minval = minval_dev;
-        c.j_blocks = (max_n + kWaves * 8 - 1) / (kWaves * 8);
-        c.i_blocks = (max_n + 16 - 1) / 16;
-        const int64_t blocks = (int64_t)n_scenes * c.j_blocks * c.i_blocks;
-        if ((st = grid_check(blocks))) return st;
-        triplet_tile_kernel<16, 8><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(c);
-        return mvm_check_launch("triplet_tile_kernel");
-    }
-    CubeArgs c{};
-    c.cam_offs = cam_offs_dev;
-    c.e = (const double *)workspace_dev;
-    c.mat_stride = mat_stride;
-    c.ld = ld;
-    c.cube_offs = cube_offs_dev;
-    c.row_offs = row_offs_dev;
-    c.cube = cube_dev;
-    c.argmin = argmin_dev;
-    c.minval = minval_dev;
-    c.i_count = max_n;
-    const int rows_per_wg = kWaves * kTripletRowsPerWave;
-    c.j_blocks = (max_n + rows_per_wg - 1) / rows_per_wg;
-    const int64_t blocks = (int64_t)n_scenes * max_n * c.j_blocks;
-    if ((st = grid_check(blocks))) return st;
-    triplet_kernel<kTripletRowsPerWave><<<dim3((unsigned)blocks), dim3(kThreads), 0, s>>>(c);
-    return mvm_check_launch("triplet_kernel");
-}
-
-}  // namespace
-
-extern "C" int mvm_triplet_cost_argmin(const double *pts_dev, const int64_t *cam_offs_dev,
-                                       const double *F_dev, int32_t n_scenes, int32_t max_n,
-                                       const int64_t *cube_offs_dev, const int64_t *row_offs_dev,
-                                       float *cube_dev, int32_t *argmin_dev, float *minval_dev,
-                                       void *workspace_dev, size_t workspace_bytes, mvm_stream_t stream) {
+int mvm_triplet_cost_argmin(const double *pts_dev, const int64_t *cam_offs_dev, const double *F_dev,
+                            int32_t n_scenes, int32_t max_n, const int64_t *cube_offs_dev,
+                            const int64_t *row_offs_dev, float *cube_dev, int32_t *argmin_dev,
+                            float *minval_dev, void *workspace_dev, size_t workspace_bytes,
+                            mvm_stream_t stream) {
     return mvm_triplet_cost_argmin_ex(pts_dev, cam_offs_dev, F_dev, n_scenes, max_n, cube_offs_dev,
                                       row_offs_dev, cube_dev, argmin_dev, minval_dev, workspace_dev,
                                       workspace_bytes, nullptr, stream);
 }
+
+}  // extern "C"

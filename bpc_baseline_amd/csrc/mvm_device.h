@@ -42,6 +42,14 @@ constexpr uint32_t kWild = 3;   // non-degenerate but non-finite / huge: generic
 
 static_assert(kChunk == kThreads, "one column line per thread per chunk");
 
+// Dispatch puts workgroup b of a grid on XCD b % 8.  The index that gives
+// each XCD a contiguous range of the grid's nblocks instead (the first
+// nblocks % 8 XCDs one block more), walked in dispatch order.
+__device__ __forceinline__ uint32_t xcd_contiguous_block(uint32_t blk, uint32_t nblocks) {
+    const uint32_t q = nblocks / 8, r = nblocks % 8, x = blk % 8;
+    return x * q + min(x, r) + blk / 8;
+}
+
 // ---------------------------------------------------------------- lines ----
 // Row side: l2 = F @ (x, y, 1)   (epipolar_matching.py:13)
 __device__ __forceinline__ bool row_line(const double f[9], double x, double y, double &l0,

@@ -8,8 +8,25 @@
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
 
 #include "mvmatch.h"
+
+// f(std::true_type) or f(std::false_type): a launch written once for both
+// values of a kernel's bool template parameter
+template <typename F>
+void dispatch_bool(bool b, F &&f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+// f(std::integral_constant<int, V>) for the V among Vs... that v equals (none:
+// f is not called): the same for an int template parameter
+template <int... Vs, typename F>
+void dispatch_int(int v, F &&f) {
+    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 int mvm_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void mvm_set_error(const char *msg);

@@ -849,16 +849,6 @@ bool aligned16(const T *...p) {
     return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
 }
 
-// f(std::true_type) or f(std::false_type): a launch written once for both
-// values of a kernel's bool template parameter
-template <typename F>
-void dispatch_bool(bool b, F &&f) {
-    if (b)
-        f(std::true_type{});
-    else
-        f(std::false_type{});
-}
-
 }  // namespace
 
 extern "C" {

@@ -286,12 +286,14 @@ def test_pairwise_argmin_only(cuda, argmin_path):
 
 # --------------------------------------------------------------- cube ----
 # largest view each forced lane shape holds (3 k: 192 at one row per
-# instruction; 5 k: 160 at two; 8 k at two rows: 256)
-KPL_MAX_VIEW = {"fused_kpl3": 192, "fused_kpl5": 160, "fused_rows2_kpl8": 256, "fused_tile32_kpl5": 160}
+# instruction; 5 / 6 / 7 k: 160 / 192 / 224 at two; 8 k at two rows: 256)
+KPL_MAX_VIEW = {"fused_kpl3": 192, "fused_kpl5": 160, "fused_kpl6": 192, "fused_kpl7": 224,
+                "fused_rows2_kpl8": 256, "fused_tile32_kpl5": 160}
 
 
 @pytest.fixture(params=["default", "small", "fused", "fused_rows2", "fused_rows1", "fused_kpl4",
-                        "fused_rows1_kpl4", "fused_kpl3", "fused_kpl5", "fused_rows2_kpl8", "fused_tile32",
+                        "fused_rows1_kpl4", "fused_kpl3", "fused_kpl5", "fused_kpl6", "fused_kpl7",
+                        "fused_rows2_kpl8", "fused_tile32",
                         "fused_tile32_kpl5", "fused_rows8_tile16", "fused_rows4", "workspace",
                         "generic"])
 def cube_path(request):
@@ -301,8 +303,8 @@ def cube_path(request):
     (i, j) rows per wave instruction (eight up to 32: rows8_tile16 with tiles of
     16 i rows, the default 32; rows4 the four-row form there) -- 3 k per lane where the view fits them
     (the default), or 4 forced (kpl4), or 3 forced (kpl3: fewer rows per
-    instruction where the view needs them; views of <= 192 only), or 5 / 8
-    forced (the split forms' wide lanes: views of <= 160 / <= 256), tiles of
+    instruction where the view needs them; views of <= 192 only), or 5 to 8
+    forced (the split forms' wide lanes: views of <= 160 / 192 / 224 / 256), tiles of
     32 i rows (tile32: the split forms; one row per instruction keeps 16) -- the
     tiled kernel over the fp64 workspace (beyond 256: the generic kernel) and
     the generic kernel."""
@@ -315,6 +317,8 @@ def cube_path(request):
                                                 "cube_cols_per_lane": 4},
                            "fused_kpl3": {"cube_kernel": "fused", "cube_cols_per_lane": 3},
                            "fused_kpl5": {"cube_kernel": "fused", "cube_cols_per_lane": 5},
+                           "fused_kpl6": {"cube_kernel": "fused", "cube_cols_per_lane": 6},
+                           "fused_kpl7": {"cube_kernel": "fused", "cube_cols_per_lane": 7},
                            "fused_rows2_kpl8": {"cube_kernel": "fused", "cube_rows_per_instr": 2,
                                                 "cube_cols_per_lane": 8},
                            "fused_tile32": {"cube_kernel": "fused", "cube_tile_rows": 32},

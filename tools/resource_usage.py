@@ -28,7 +28,9 @@ if out.returncode:
     sys.exit("\n".join(l for l in out.stderr.splitlines() if "error" in l)[:3000])
 rows, cur = [], None
 for line in out.stderr.splitlines():
-    m = re.search(r"remark: (?:\s*)([^:\[]+?): (\S+) \[", line)
+    # the key may hold a unit in brackets ("ScratchSize [bytes/lane]"): only
+    # the remark's own trailing "[-Rpass-analysis=...]" ends the value
+    m = re.search(r"remark:\s*([^:]+?): (\S+) \[-R", line)
     if not m:
         continue
     key, val = m.group(1).strip(), m.group(2)
