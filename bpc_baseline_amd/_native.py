@@ -191,6 +191,17 @@ SIGNATURES = {
         _vp, _vp, _i32, _i32,               # match_offs, count, n_scenes, n_cams
         _vp, _vp, _vp, ctypes.c_double,     # pts, cam_offs, proj, gate
         _vp, _vp, _vp, _vp, _vp]),          # views, ext_cost, X (in/out), pruned (out), stream
+    "mvm_mark_used": (ctypes.c_int, [
+        _vp, _vp, _vp, _i64, _i32, _i32,    # views, match_offs, count, n_rows, n_scenes, n_cams
+        _i32, _i32, _i32,                   # seed_a, seed_b, seed_c
+        _vp, _vp, _vp, _i64, _vp, _vp]),    # sub_cam_offs, orig (both may be NULL), cam_offs, n_det, used, stream
+    "mvm_leftover_counts": (ctypes.c_int, [
+        _vp, _vp, _i32, _i32,               # used, cam_offs, n_scenes, n_cams
+        _i32, _i32, _i32, _vp, _vp]),       # seed_a, seed_b, seed_c, counts (out), stream
+    "mvm_leftover_gather": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp,            # used, pts, boxes, cam_offs, sub_cam_offs
+        _i32, _i32, _i32, _i32, _i32,       # n_scenes, n_cams, seed_a, seed_b, seed_c
+        _vp, _vp, _vp, _vp]),               # pts, boxes, orig (out), stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -17,6 +17,9 @@
 //  * mvm_rig_matrices: compute_fundamental_matrix (camera_utils.py:23-46) per
 //    (capture, pair) and P = K @ RT[:3] (process_pose.py:91) per (capture,
 //    camera) for pinhole K, so a batch whose rigs differ needs no host numpy.
+//  * mvm_mark_used, mvm_leftover_counts, mvm_leftover_gather: the sub-batch of
+//    an extra seed pass over a C-camera batch: the detections no
+//    earlier match holds, compacted per view in order, cameras reordered.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -842,11 +845,155 @@ __global__ __launch_bounds__(kRigThreads) void rig_matrices_kernel(
     }
 }
 
+// ------------------------------------------------- leftovers ----
+// The sub-batch of an extra seed pass: the detections no match
+// of an earlier pass holds, per view in ascending index order, with the
+// cameras reordered so that the pass's seed triple comes first.  `order`
+// packs that camera order pi, four bits a slot: slot q reads camera
+// (order >> 4 q) & 15.
+
+constexpr int kMarkThreads = 256;
+
+__device__ __forceinline__ int order_cam(uint32_t order, int q) { return (int)(order >> (4 * q) & 15u); }
+
+// One thread per (match row, slot): used[cam_offs[s C + pi[q]] + l] = 1 for the
+// row's detection l of slot q.  The row's capture is found by bisection of
+// match_offs; rows at and beyond count[s] mark nothing.  With sub_offs / orig
+// (a later pass) l indexes the pass's own view and orig maps it to the
+// original one.  Every index is range-checked against its view (and the flag
+// array) before it is used.  Plain vector stores of the same value: threads
+// that meet on a flag write what is already being written.
+__global__ __launch_bounds__(kMarkThreads) void mark_used_kernel(
+    const int32_t *__restrict__ views, const int64_t *__restrict__ match_offs,
+    const int32_t *__restrict__ count, const int64_t *__restrict__ sub_offs,
+    const int32_t *__restrict__ orig, const int64_t *__restrict__ cam_offs, int64_t n_rows,
+    int32_t n_scenes, int32_t n_cams, uint32_t order, int64_t n_det, int32_t *__restrict__ used) {
+    const int64_t t = (int64_t)blockIdx.x * kMarkThreads + threadIdx.x;
+    const int64_t row = t / n_cams;
+    const int q = (int)(t - row * n_cams);
+    if (row >= n_rows || row < match_offs[0]) return;
+    int32_t lo = 0, hi = n_scenes;          // match_offs[lo] <= row, the last such capture
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (match_offs[mid] <= row)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int64_t s = lo;
+    const int64_t w = row - match_offs[s];
+    if (w >= min<int64_t>(count[s], match_offs[s + 1] - match_offs[s])) return;
+    int64_t v = views[row * n_cams + q];
+    if (sub_offs) {
+        const int64_t so = sub_offs[s * n_cams + q];
+        if (v < 0 || v >= sub_offs[s * n_cams + q + 1] - so) return;
+        v = orig[so + v];
+    }
+    const int c = order_cam(order, q);
+    const int64_t o = cam_offs[s * n_cams + c];
+    if (v < 0 || v >= cam_offs[s * n_cams + c + 1] - o) return;
+    const int64_t k = o + v;
+    if (k < 0 || k >= n_det) return;
+    used[k] = 1;
+}
+
+// One wave per (capture, slot), four to a workgroup (its index a scalar): the
+// leftovers of camera pi[q], counted by ballot + popcount over 64-detection
+// chunks -- the walk of leftover_gather_kernel, so the two agree on every
+// view by construction.  No LDS, no barrier.
+__global__ __launch_bounds__(kCompactThreads) void leftover_count_kernel(
+    const int32_t *__restrict__ used, const int64_t *__restrict__ cam_offs, int64_t n_views,
+    int32_t n_cams, uint32_t order, int32_t *__restrict__ counts) {
+    const int lane = threadIdx.x % 64;
+    const int64_t sq = (int64_t)blockIdx.x * kCompactScenes +
+                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    if (sq >= n_views) return;
+    const int64_t s = sq / n_cams;
+    const int c = order_cam(order, (int)(sq - s * n_cams));
+    const int64_t b = cam_offs[s * n_cams + c], e = cam_offs[s * n_cams + c + 1];
+    int32_t n = 0;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+        const int64_t k = k0 + lane;
+        n += __builtin_popcountll(__ballot(k < e && used[k] == 0));
+    }
+    if (lane == 0) counts[sq] = n;
+}
+
+// The same wave per (capture, slot): leftover l of the chunk goes to row
+// sub_offs[s C + q] + base + (leftovers of the chunk in lower lanes), `base`
+// the scalar count of the chunks before -- input order is kept.  A row is a
+// 16-byte centroid, a 16-byte box and the detection's index in its original
+// view.  Never more rows than sub_offs leaves the view.  VEC: 16-byte
+// accesses (every base 16-byte aligned).
+template <bool VEC>
+__global__ __launch_bounds__(kCompactThreads) void leftover_gather_kernel(
+    const int32_t *__restrict__ used, const double *__restrict__ pts,
+    const int32_t *__restrict__ boxes, const int64_t *__restrict__ cam_offs,
+    const int64_t *__restrict__ sub_offs, int64_t n_views, int32_t n_cams, uint32_t order,
+    double *__restrict__ pts_out, int32_t *__restrict__ boxes_out, int32_t *__restrict__ orig_out) {
+    const int lane = threadIdx.x % 64;
+    const int64_t sq = (int64_t)blockIdx.x * kCompactScenes +
+                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    if (sq >= n_views) return;
+    const int64_t s = sq / n_cams;
+    const int c = order_cam(order, (int)(sq - s * n_cams));
+    const int64_t b = cam_offs[s * n_cams + c], e = cam_offs[s * n_cams + c + 1];
+    const int64_t dst = sub_offs[sq], room = sub_offs[sq + 1] - dst;
+    int64_t base = 0;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+        const int64_t k = k0 + lane;
+        const bool keep = k < e && used[k] == 0;
+        const uint64_t m = __ballot(keep);
+        const int64_t pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < room) {
+            const int64_t r = dst + pos;
+            if (VEC) {
+                reinterpret_cast<double2 *>(pts_out)[r] = reinterpret_cast<const double2 *>(pts)[k];
+                reinterpret_cast<int4 *>(boxes_out)[r] = reinterpret_cast<const int4 *>(boxes)[k];
+            } else {
+                pts_out[2 * r] = pts[2 * k];
+                pts_out[2 * r + 1] = pts[2 * k + 1];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) boxes_out[4 * r + j] = boxes[4 * k + j];
+            }
+            orig_out[r] = (int32_t)(k - b);
+        }
+        base += __builtin_popcountll(m);
+    }
+}
+
 // ---- host: launch helpers -------------------------------------------------------
 // every pointer on a 16-byte boundary (what the VEC kernels' 16-byte accesses need)
 template <typename... T>
 bool aligned16(const T *...p) {
     return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// The camera order of a seed pass, packed as the leftover kernels read it:
+// (a, b, c), then the other cameras ascending.  MVM_OK, or the refusal of
+// n_cams outside 4..MVM_MAX_CAMS or of a triple that is not three distinct
+// cameras < n_cams.
+int leftover_order(int32_t n_cams, int32_t a, int32_t b, int32_t c, uint32_t &order) {
+    if (n_cams < 4 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [4, %d]", n_cams, MVM_MAX_CAMS);
+    const int32_t seed[3] = {a, b, c};
+    for (int k = 0; k < 3; ++k)
+        if (seed[k] < 0 || seed[k] >= n_cams)
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "seed (%d, %d, %d): camera %d outside [0, %d)", a, b,
+                            c, seed[k], n_cams);
+    if (a == b || a == c || b == c)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "seed (%d, %d, %d): a camera is repeated", a, b, c);
+    order = (uint32_t)a | (uint32_t)b << 4 | (uint32_t)c << 8;
+    int q = 3;
+    for (int32_t d = 0; d < n_cams; ++d)
+        if (d != a && d != b && d != c) order |= (uint32_t)d << (4 * q++);
+    return MVM_OK;
+}
+
+// workgroups of a wave per (capture, slot) launch, or -1 beyond one launch
+int64_t leftover_grid(int32_t n_scenes, int32_t n_cams) {
+    const int64_t grid = ((int64_t)n_scenes * n_cams + kCompactScenes - 1) / kCompactScenes;
+    return grid > kMaxGridBlocks ? -1 : grid;
 }
 
 }  // namespace
@@ -988,6 +1135,87 @@ int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *co
         match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, gate, n_scenes, n_cams, views_dev,
         ext_cost_dev, X_dev, pruned_dev);
     return mvm_check_launch("prune_views_kernel");
+}
+
+int mvm_mark_used(const int32_t *views_dev, const int64_t *match_offs_dev, const int32_t *count_dev,
+                  int64_t n_rows, int32_t n_scenes, int32_t n_cams, int32_t seed_a, int32_t seed_b,
+                  int32_t seed_c, const int64_t *sub_cam_offs_dev, const int32_t *orig_dev,
+                  const int64_t *cam_offs_dev, int64_t n_det, int32_t *used_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    if (n_rows < 0 || n_det < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_rows or n_det");
+    uint32_t order = 0;
+    if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
+    if ((sub_cam_offs_dev == nullptr) != (orig_dev == nullptr))
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "sub_cam_offs_dev and orig_dev go together");
+    if (n_rows == 0 || n_det == 0) return MVM_OK;
+    if (const int st = mvm_require_ptrs({{views_dev, "views_dev"},
+                                         {match_offs_dev, "match_offs_dev"},
+                                         {count_dev, "count_dev"},
+                                         {cam_offs_dev, "cam_offs_dev"},
+                                         {used_dev, "used_dev"}}))
+        return st;
+    const int64_t grid = (n_rows * n_cams + kMarkThreads - 1) / kMarkThreads;
+    if (grid > kMaxGridBlocks)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_rows=%lld: more rows than one launch holds; split them",
+                        (long long)n_rows);
+    mark_used_kernel<<<(unsigned)grid, kMarkThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        views_dev, match_offs_dev, count_dev, sub_cam_offs_dev, orig_dev, cam_offs_dev, n_rows, n_scenes,
+        n_cams, order, n_det, used_dev);
+    return mvm_check_launch("mark_used_kernel");
+}
+
+int mvm_leftover_counts(const int32_t *used_dev, const int64_t *cam_offs_dev, int32_t n_scenes,
+                        int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
+                        int32_t *counts_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    uint32_t order = 0;
+    if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
+    if (const int st = mvm_require_ptrs(
+            {{used_dev, "used_dev"}, {cam_offs_dev, "cam_offs_dev"}, {counts_dev, "counts_dev"}}))
+        return st;
+    const int64_t grid = leftover_grid(n_scenes, n_cams);
+    if (grid < 0)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more views than one launch holds; split them",
+                        n_scenes);
+    leftover_count_kernel<<<(unsigned)grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        used_dev, cam_offs_dev, (int64_t)n_scenes * n_cams, n_cams, order, counts_dev);
+    return mvm_check_launch("leftover_count_kernel");
+}
+
+int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const int32_t *boxes_dev,
+                        const int64_t *cam_offs_dev, const int64_t *sub_cam_offs_dev, int32_t n_scenes,
+                        int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
+                        double *pts_out_dev, int32_t *boxes_out_dev, int32_t *orig_out_dev,
+                        mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    uint32_t order = 0;
+    if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
+    if (const int st = mvm_require_ptrs({{used_dev, "used_dev"},
+                                         {pts_dev, "pts_dev"},
+                                         {boxes_dev, "boxes_dev"},
+                                         {cam_offs_dev, "cam_offs_dev"},
+                                         {sub_cam_offs_dev, "sub_cam_offs_dev"},
+                                         {pts_out_dev, "pts_out_dev"},
+                                         {boxes_out_dev, "boxes_out_dev"},
+                                         {orig_out_dev, "orig_out_dev"}}))
+        return st;
+    const int64_t grid = leftover_grid(n_scenes, n_cams);
+    if (grid < 0)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more views than one launch holds; split them",
+                        n_scenes);
+    dispatch_bool(aligned16(pts_dev, boxes_dev, pts_out_dev, boxes_out_dev), [&](auto vec) {
+        leftover_gather_kernel<decltype(vec)::value>
+            <<<(unsigned)grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+                used_dev, pts_dev, boxes_dev, cam_offs_dev, sub_cam_offs_dev, (int64_t)n_scenes * n_cams,
+                n_cams, order, pts_out_dev, boxes_out_dev, orig_out_dev);
+    });
+    return mvm_check_launch("leftover_gather_kernel");
 }
 
 int mvm_pack_detections(const float *boxes_dev, const float *conf_dev, const float *cls_dev,

@@ -289,7 +289,9 @@ def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
     ``match_captures`` (``keep_cube``, the thresholds, ``F``, ``proj``,
     ``n_cams``, ...); ``reproj`` in it goes to ``MatchBatch.table`` instead
     (True: a three-camera table with reprojection residuals; a table of
-    n_cams > 3 always has them).
+    n_cams > 3 always has them).  ``extra_seeds`` raises
+    ``NotImplementedError``: the gather does not carry ``table_all()``'s
+    ``seed_pass``.
     ``split``: a dict that receives this rank's seconds in "chain", "table"
     and "gather" (synchronising after each, so only for measurements).
     -> the ``MatchTable`` of all captures on rank 0, None elsewhere."""
@@ -308,6 +310,11 @@ def match_captures_sharded(env: DistEnv, boxes, conf, cls, img_offs, Ks, RTs, *,
 
     C = int(kw.get("n_cams", 3))
     reproj = kw.pop("reproj", None)
+    if kw.get("extra_seeds") is not None:
+        # gather_tables fixes the optional field set by MatchTable.VIEW_FIELDS;
+        # table_all()'s seed_pass is not among them
+        raise NotImplementedError("match_captures_sharded does not take extra_seeds: the table gather "
+                                  "does not carry the merged table's seed_pass")
     if not 3 <= C <= 8:
         raise ValueError(f"n_cams: expected 3..8, got {C}")
     n_img = int(img_offs.numel()) - 1

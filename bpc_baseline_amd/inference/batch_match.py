@@ -134,6 +134,16 @@ class MatchBatch:
     # view of camera d was dropped for its reprojection residual (0 in every
     # row of a three-camera batch); None without a gate
     pruned: Optional[torch.Tensor] = None         # int32 [cap]
+    # match_captures(extra_seeds=[...]): the results of the
+    # extra seed passes hang off the first pass's batch, in order.  Each is a
+    # batch of its own over the detections the passes before it left, with the
+    # cameras in ``cam_order`` (view slot q is original camera cam_order[q]; the
+    # seed triple first) and ``orig`` naming each of its detections' index in
+    # its original view.  Both are None on the first pass's batch, whose
+    # fields the extra passes never touch.
+    cam_order: Optional[tuple] = None
+    orig: Optional[torch.Tensor] = None           # int32 [n]
+    passes: tuple = ()
 
     def host(self) -> dict:
         """One D2H copy of everything ``predictions`` reads (and ``pruned``
@@ -209,6 +219,69 @@ class MatchBatch:
         return MatchTable(scene=scene[:n], match=match[:n], cost=cost[:n], X=X[:n], boxes=boxes[:n],
                           centroids=cent[:n], offs=offs)
 
+    def _table_in_original_order(self) -> "MatchTable":
+        """``table(reproj=True)`` of an extra pass with its per-camera columns
+        back in original camera order and its views naming original
+        detections (torch indexing on the device; no host sync)."""
+        tab = self.table(reproj=True)
+        if self.cam_order is None:
+            return tab
+        C, dev = self.n_cams, self.match.device
+        inv = np.argsort(np.asarray(self.cam_order, np.int64))       # inv[cam_order[q]] = q
+        inv_dev, seed_dev = ops._h2d_int64([inv, np.asarray(self.cam_order[:3], np.int64)], dev)
+        views = tab.views
+        if int(views.shape[0]):
+            cam = self.cam_offs_dev
+            if cam is None:
+                cam, = ops._h2d_int64([self.cam_offs], dev)
+            slot = tab.scene.to(torch.int64)[:, None] * C + torch.arange(C, device=dev)[None, :]
+            rows = cam[slot] + views.clamp(min=0).to(torch.int64)
+            # a slot with no detection (-1) stays as it is
+            views = torch.where(views >= 0, self.orig[rows.clamp(max=max(int(self.orig.numel()) - 1, 0))],
+                                views)
+        views = views.index_select(1, inv_dev)
+        return MatchTable(scene=tab.scene, match=views.index_select(1, seed_dev), cost=tab.cost, X=tab.X,
+                          boxes=tab.boxes.index_select(1, inv_dev),
+                          centroids=tab.centroids.index_select(1, inv_dev), offs=tab.offs, views=views,
+                          n_views=tab.n_views, ext_cost=tab.ext_cost,
+                          reproj=tab.reproj.index_select(1, inv_dev), n_cams=C)
+
+    def table_all(self, scene_base: int = 0) -> "MatchTable":
+        """The matches of every pass as one ``MatchTable`` in original camera
+        order (``match_captures(extra_seeds=...)``): per
+        capture the first pass's rows, then the second's, and so on, each
+        pass in its own order.  Every pass's ``table(reproj=True)`` is built
+        on the device; the per-camera columns (``boxes``, ``centroids``,
+        ``views``, ``reproj``) of an extra pass are put back in original
+        camera order and its ``views`` go through its ``orig``, so they name
+        the detections of the first pass's ``pts`` / ``boxes``.  ``ext_cost``
+        stays in the slot order of its pass (column e belongs to camera
+        ``cam_order[3 + e]``).  ``seed_pass`` int32 [n] holds the pass index;
+        ``match`` of a row with ``seed_pass > 0`` holds the detections of the
+        pass's seed triple (original indices, the triple's order), so
+        ``views[:, :3] == match`` holds only where ``seed_pass == 0``.  No
+        host sync.  A batch without extra passes gives ``table(reproj=True)``
+        with ``seed_pass`` all zero."""
+        tabs = [b._table_in_original_order() for b in (self,) + tuple(self.passes)]
+        dev = self.match.device
+        counts = np.stack([np.diff(np.asarray(t.offs, np.int64)) for t in tabs])      # [passes, S]
+        base = np.concatenate([[0], np.cumsum(counts.sum(axis=1))[:-1]])
+        offs = np.zeros(counts.shape[1] + 1, np.int64)
+        np.cumsum(counts.sum(axis=0), out=offs[1:])
+        # row r of the merged table: capture by capture, pass by pass
+        src = [np.arange(base[p] + t.offs[s], base[p] + t.offs[s + 1])
+               for s in range(counts.shape[1]) for p, t in enumerate(tabs)]
+        src = np.concatenate(src).astype(np.int64) if src else np.zeros(0, np.int64)
+        which = np.repeat(np.arange(len(tabs)), counts.sum(axis=1))[src] if src.size else np.zeros(0, np.int64)
+        if src.size:
+            src_dev, which_dev = ops._h2d_int64([src, which], dev)
+        else:
+            src_dev = which_dev = torch.zeros(0, dtype=torch.int64, device=dev)
+        take = lambda k: torch.cat([getattr(t, k) for t in tabs]).index_select(0, src_dev)
+        out = {k: take(k) for k in MatchTable.FIELDS + MatchTable.VIEW_FIELDS}
+        out["scene"] = out["scene"] + int(scene_base)
+        return MatchTable(offs=offs, n_cams=self.n_cams, seed_pass=which_dev.to(torch.int32), **out)
+
 
 @dataclass
 class MatchTable:
@@ -233,14 +306,20 @@ class MatchTable:
     ext_cost: Optional[torch.Tensor] = None   # float32 [n, C - 3]
     reproj: Optional[torch.Tensor] = None     # float64 [n, C]   pixels
     n_cams: int = 3
+    # a table made by MatchBatch.table_all: the seed pass the row came from
+    # (0: cameras 0-2).  Where it is > 0, ``match`` holds the detections of
+    # that pass's seed triple, not views[:, :3], and ext_cost is in the slot
+    # order of that pass
+    seed_pass: Optional[torch.Tensor] = None  # int32 [n]
 
     FIELDS = ("scene", "match", "cost", "X", "boxes", "centroids")
     VIEW_FIELDS = ("views", "n_views", "ext_cost", "reproj")
 
     def fields(self) -> tuple:
         """The names of the row fields this table holds: ``FIELDS``, then
-        those of ``VIEW_FIELDS`` that are set."""
-        return self.FIELDS + tuple(k for k in self.VIEW_FIELDS if getattr(self, k) is not None)
+        those of ``VIEW_FIELDS`` that are set, then ``seed_pass`` if set."""
+        return (self.FIELDS + tuple(k for k in self.VIEW_FIELDS if getattr(self, k) is not None)
+                + (("seed_pass",) if self.seed_pass is not None else ()))
 
     @classmethod
     def empty(cls, device, offs: Optional[np.ndarray] = None, n_cams: int = 3,
@@ -297,7 +376,8 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    keep_cube: bool = False, timings: Optional[dict] = None,
                    F: Optional[torch.Tensor] = None,
                    proj: Optional[torch.Tensor] = None, rig: str = "host",
-                   n_cams: int = 3, reproj_gate: Optional[float] = None) -> MatchBatch:
+                   n_cams: int = 3, reproj_gate: Optional[float] = None,
+                   extra_seeds: Optional[Sequence] = None) -> MatchBatch:
     """Detect-packing + matching + triangulation of S 3-camera captures.
 
     ``boxes`` f32 [n, 4] xyxy, ``conf``/``cls`` f32 [n]: the detector outputs
@@ -348,12 +428,34 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     ``ext_cost``; the result's ``pruned`` holds bit d where camera d was
     dropped.  Cameras 0-2, the matches, their costs, order and counts never
     change.  With ``n_cams=3`` the gate is accepted and ``pruned`` is zeros.
+
+    ``extra_seeds`` = [(a, b, c), ...], 1 to 4 triples of distinct cameras
+    < C, needs C >= 4 (None, the default: nothing launched, today's result):
+    an object that one of cameras 0-2 misses can never become a match above,
+    so after that first pass each triple in turn runs the same C-camera path
+    on the detections no earlier pass's match holds (read after that pass's
+    gate: a pruned view is free again), with the cameras reordered so that
+    (a, b, c) are matched as the cube's N, M, P axes and the others extend
+    them.  The sub-batch is built on the device
+    (``ops_views.mark_used`` / ``leftover_counts`` / ``leftover_gather``); a
+    pass adds one device -> host copy, of its leftover counts, to those of
+    the path it runs.  The passes' results are ``MatchBatch.passes``, each a
+    batch of its own with ``cam_order`` / ``orig``; the first pass's fields
+    are byte for byte those of the call without the keyword, and
+    ``MatchBatch.table_all()`` merges all passes into one table in original
+    camera order.  ``ValueError`` for a bad triple or ``n_cams=3``;
+    ``TypeError`` with ``F`` / ``proj``, since a pass needs the F and P of
+    its own pair list.
     """
     C = _check_n_cams(n_cams)
     _check_rig(rig)
     gate = None if reproj_gate is None else ops_views._check_gate(reproj_gate)
     if rig != "host" and (F is not None or proj is not None):
         raise TypeError(f"F / proj cannot be passed with rig={rig!r}: that path computes them")
+    seeds = _check_extra_seeds(extra_seeds, C)
+    if seeds and (F is not None or proj is not None):
+        raise TypeError("F / proj cannot be passed with extra_seeds: every pass computes those of its "
+                        "own camera order")
     dev = boxes.device
     import time
     clock = [time.perf_counter()]
@@ -382,23 +484,10 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     pts, cam_offs, boxes_int, counts, status = ops.pack_detections(boxes, conf, cls, img_offs,
                                                                    conf_thresh)
     mark("pack")
-    rig_status = None
-    if rig == "device":
-        # F and P of every capture by one launch behind the packing; its
-        # per-capture status rides on the count copy below (no extra sync)
-        F, proj, rig_status = ops.rig_matrices(Ks, RTs, pairs=extension_pairs(C) if C > 3 else None,
-                                               device=dev)
-        mark("F+P device")
-    else:
-        # host work while the packing runs: F and P for every capture (once per
-        # distinct rig)
-        if F is None or proj is None:
-            F_h, P_h = _host_rig(Ks, RTs, C)
-            if F is None:
-                F = torch.from_numpy(F_h).to(dev)
-            if proj is None:
-                proj = torch.from_numpy(P_h).to(dev)
-        mark("F+P host")
+    # F and P of every capture: on the device by one launch behind the packing
+    # (its per-capture status rides on the count copy below: no extra sync), or
+    # host work while the packing runs
+    F, proj, rig_status = _rig_launch(Ks, RTs, C, rig, dev, F, proj, mark)
     F_dev = F.reshape(-1)
 
     # one device -> host copy: the kept counts and the packing status (and the
@@ -407,17 +496,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     ch = ch.cpu().numpy().astype(np.int64)
     if rig_status is not None:
         ch, rig_bad = ch[:n_img + 1], np.nonzero(ch[n_img + 1:])[0]
-        if rig_bad.size and on_device:
-            raise ValueError(f"captures {rig_bad[:8].tolist()} have a K outside the pinhole form "
-                             "mvm_rig_matrices inverts; pass Ks / RTs as host arrays (those captures "
-                             "are then computed on the host) or use rig='host'")
-        if rig_bad.size:
-            # the kernel left those captures' rows unwritten: the host's values
-            F_h, P_h = _host_rig(Ks[rig_bad], RTs[rig_bad], C)
-            idx, = ops._h2d_int64([rig_bad], dev)
-            F.view(S, 9 * n_pairs).index_copy_(0, idx,
-                                               torch.from_numpy(F_h.reshape(-1, 9 * n_pairs)).to(dev))
-            proj.index_copy_(0, idx, torch.from_numpy(P_h).to(dev))
+        _rig_fallback(F, proj, rig_bad, Ks, RTs, S, C, on_device, dev)
     counts_host = ch[:-1]
     if ch[-1] != 0:
         raise ValueError("detector box with a non-finite or out-of-range coordinate")
@@ -427,6 +506,112 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
 
     threshold = float(matching_threshold)
     full = _Rig(pts, cam_offs, cam_offs_host, counts_host.reshape(S, C), F_dev, proj)
+    out = _match_rig(full, boxes_int, S, C, threshold, keep_cube, gate, mark)
+    if seeds:
+        out.passes = _seed_passes(out, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, mark)
+    return out
+
+
+def _check_extra_seeds(extra_seeds, C: int) -> tuple:
+    """``match_captures``' extra_seeds as a tuple of triples (empty: None)."""
+    if extra_seeds is None:
+        return ()
+    if C < 4:
+        raise ValueError(f"extra_seeds needs n_cams >= 4, got n_cams={C}")
+    seeds = tuple(ops_views._check_seed(seed, C) for seed in extra_seeds)
+    if not 1 <= len(seeds) <= 4:
+        raise ValueError(f"extra_seeds: expected 1 to 4 triples, got {len(seeds)}")
+    return seeds
+
+
+def _rig_launch(Ks, RTs, C, rig, dev, F, proj, mark):
+    """F and P of every capture where ``rig`` says (what of ``F`` / ``proj`` is
+    passed in is kept) -> (F, proj, the device rig's per-capture status or None)."""
+    if rig == "device":
+        F, proj, rig_status = ops.rig_matrices(Ks, RTs, pairs=extension_pairs(C) if C > 3 else None,
+                                               device=dev)
+        mark("F+P device")
+        return F, proj, rig_status
+    # once per distinct rig
+    if F is None or proj is None:
+        F_h, P_h = _host_rig(Ks, RTs, C)
+        if F is None:
+            F = torch.from_numpy(F_h).to(dev)
+        if proj is None:
+            proj = torch.from_numpy(P_h).to(dev)
+    mark("F+P host")
+    return F, proj, None
+
+
+def _rig_fallback(F, proj, rig_bad, Ks, RTs, S, C, on_device, dev) -> None:
+    """The captures ``rig_bad`` whose K the device rig refused: their rows of
+    ``F`` / ``proj`` from the host, in place."""
+    if rig_bad.size and on_device:
+        raise ValueError(f"captures {rig_bad[:8].tolist()} have a K outside the pinhole form "
+                         "mvm_rig_matrices inverts; pass Ks / RTs as host arrays (those captures "
+                         "are then computed on the host) or use rig='host'")
+    if rig_bad.size:
+        # the kernel left those captures' rows unwritten: the host's values
+        n_pairs = 3 + 3 * (C - 3)
+        F_h, P_h = _host_rig(Ks[rig_bad], RTs[rig_bad], C)
+        idx, = ops._h2d_int64([rig_bad], dev)
+        F.view(S, 9 * n_pairs).index_copy_(0, idx,
+                                           torch.from_numpy(F_h.reshape(-1, 9 * n_pairs)).to(dev))
+        proj.index_copy_(0, idx, torch.from_numpy(P_h).to(dev))
+
+
+def _seed_passes(first: MatchBatch, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, mark) -> tuple:
+    """The extra seed passes behind the first: per triple the
+    leftovers of every view as a sub-batch in the triple's camera order, F and
+    P of the reordered rig by the call's ``rig`` path, and ``_match_rig`` on
+    it.  One device -> host copy a pass beside ``_match_rig``'s: the leftover
+    counts (the device rig's status rides on it)."""
+    dev = first.pts.device
+    full_offs = first.cam_offs_dev
+    used = torch.zeros(int(first.pts.shape[0]), dtype=torch.int32, device=dev)
+    ops_views.mark_used(first.views, first.offs_dev, first.count_dev, full_offs, used, C)
+    mark("mark used")
+    passes = []
+    for p, seed in enumerate(seeds, 1):
+        mark_p = lambda name, p=p: mark(f"pass {p}: {name}")
+        order = ops_views.seed_order(seed, C)
+        counts = ops_views.leftover_counts(used, full_offs, C, seed)
+        mark_p("leftover counts")
+        sel = list(order)
+        Kp, RTp = Ks[:, sel], RTs[:, sel]
+        if not isinstance(Kp, torch.Tensor):
+            Kp, RTp = np.ascontiguousarray(Kp), np.ascontiguousarray(RTp)
+        F, proj, rig_status = _rig_launch(Kp, RTp, C, rig, dev, None, None, mark_p)
+        ch = torch.cat([counts] + ([rig_status] if rig_status is not None else []))
+        ch = ch.cpu().numpy().astype(np.int64)
+        if rig_status is not None:
+            _rig_fallback(F, proj, np.nonzero(ch[S * C:])[0], Kp, RTp, S, C, on_device, dev)
+        sub_counts = ch[:S * C]
+        sub_offs = np.zeros(S * C + 1, np.int64)
+        np.cumsum(sub_counts, out=sub_offs[1:])
+        mark_p("leftover counts D2H")
+        sub_offs_dev, = ops._h2d_int64([sub_offs], dev)
+        pts, boxes, orig = ops_views.leftover_gather(used, first.pts, first.boxes, full_offs, sub_offs_dev,
+                                                     C, seed, int(sub_offs[-1]))
+        mark_p("leftover gather")
+        sub = _Rig(pts, sub_offs_dev, sub_offs, sub_counts.reshape(S, C), F.reshape(-1), proj)
+        res = _match_rig(sub, boxes, S, C, threshold, False, gate, mark_p, cam_order=order, orig=orig)
+        passes.append(res)
+        if p < len(seeds):
+            ops_views.mark_used(res.views, res.offs_dev, res.count_dev, full_offs, used, C, seed,
+                                sub_offs_dev, orig)
+            mark_p("mark used")
+    return tuple(passes)
+
+
+def _match_rig(full: _Rig, boxes_int, S, C, threshold, keep_cube, gate, mark, **fields) -> MatchBatch:
+    """What follows the count copy: the three-camera chain on the first three
+    views of ``full``, the extension into the others, the gate if set ->
+    the ``MatchBatch`` (``fields``: further fields of it)."""
+    pts = full.pts
+    dev = pts.device
+    counts_host = full.counts.reshape(-1)
+    n_pairs = 3 + 3 * (C - 3)
     three = full
     if C > 3:
         # cameras 0, 1, 2 of every capture as a three-camera batch of its own
@@ -468,7 +653,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                       pts=full.pts, boxes=boxes_int, cam_offs=full.cam_offs_host,
                       cube=res.cube if keep_cube else None, offs_dev=res.offs_dev, count_dev=res.count,
                       cam_offs_dev=full.cam_offs, views=views, ext_cost=ext_cost, n_cams=C,
-                      proj=full.proj.reshape(S, C, 3, 4), pruned=pruned)
+                      proj=full.proj.reshape(S, C, 3, 4), pruned=pruned, **fields)
 
 
 def _extend(full: _Rig, res: _Chain, count_h, S, C, threshold, mark):
@@ -656,6 +841,8 @@ def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3, r
 
     ``n_cams`` (in ``kwargs``) is passed through; the worker processes compute
     three-camera rigs, so a stream of n_cams > 3 computes F / P inline.
+    ``extra_seeds`` is passed through as well (it needs n_cams > 3, so that
+    inline path).
     """
     if "F" in kwargs or "proj" in kwargs:
         raise TypeError("match_capture_stream computes F and proj itself")

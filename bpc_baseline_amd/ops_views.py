@@ -1,17 +1,21 @@
-"""The view-pruning op over the C ABI (``torch.ops.mvmatch_views.*``).
+"""The ops on the views of a C-camera batch over the C ABI
+(``torch.ops.mvmatch_views.*``).
 
 ``bpc_baseline_amd.ops`` keeps its frozen op surface (``mvmatch::*_out``); the
-op that acts on the views of a C-camera batch after the fact registers here,
-under a namespace of its own, with the same boundary layer: spec rows checked
+ops that act on the views of a C-camera batch after the fact register here,
+under a namespace of their own, with the same boundary layer: spec rows checked
 by ``ops._check_args``, the C entry point through ``ops._call``, and the shared
 fake that returns None.
 
-  mvmatch_views::prune_views_out   mvm_prune_views_triangulate
+  mvmatch_views::prune_views_out       mvm_prune_views_triangulate
+  mvmatch_views::mark_used_out         mvm_mark_used               
+  mvmatch_views::leftover_counts_out   mvm_leftover_counts
+  mvmatch_views::leftover_gather_out   mvm_leftover_gather
 """
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import List, Optional
 
 import torch
 from torch import Tensor
@@ -19,7 +23,7 @@ from torch import Tensor
 from . import _native, ops
 from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64
 
-__all__ = ["prune_views"]
+__all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather"]
 
 
 def _check_gate(gate) -> float:
@@ -57,6 +61,136 @@ def prune_views_out(views: Tensor, ext_cost: Tensor, X: Tensor, match_offs: Tens
     ops._call("mvm_prune_views_triangulate", ops._p(match_offs), ops._p(count), n_scenes, n_cams,
               ops._p(pts), ops._p(cam_offs), ops._p(proj), gate, ops._p(views), ops._p(ext_cost),
               ops._p(X), ops._p(pruned), ops._stream(views))
+
+
+def _check_seed(seed, n_cams: int) -> tuple:
+    """A seed triple of ``n_cams`` cameras as three ints, or ValueError."""
+    if not 4 <= int(n_cams) <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 4..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    try:
+        seed = tuple(int(c) for c in seed)
+    except TypeError:
+        raise ValueError(f"seed: expected three cameras, got {seed!r}") from None
+    if len(seed) != 3 or len(set(seed)) != 3 or not all(0 <= c < n_cams for c in seed):
+        raise ValueError(f"seed: expected three distinct cameras < {n_cams}, got {seed}")
+    return seed
+
+
+def seed_order(seed, n_cams: int) -> tuple:
+    """The camera order of a seed pass: the triple, then the other cameras ascending."""
+    seed = _check_seed(seed, n_cams)
+    return seed + tuple(c for c in range(int(n_cams)) if c not in seed)
+
+
+@ops._gpu_op("mark_used_out", ("used",), namespace="mvmatch_views")
+def mark_used_out(views: Tensor, match_offs: Tensor, count: Tensor, n_cams: int, seed: List[int],
+                  sub_cam_offs: Optional[Tensor], orig: Optional[Tensor], cam_offs: Tensor,
+                  used: Tensor) -> None:
+    """used[detection] = 1 for every detection a match row holds (mvm_mark_used)."""
+    dev = ops._gpu(views, "views", "leftover marking")
+    seed = _check_seed(seed, n_cams)
+    if views.dim() != 2 or views.shape[1] != n_cams:
+        raise ValueError(f"views must be [cap, {n_cams}]")
+    if (sub_cam_offs is None) != (orig is None):
+        raise ValueError("sub_cam_offs and orig go together")
+    cap, n_scenes = int(views.shape[0]), count.numel()
+    rows = [(views, "views", i32, n_cams * cap, EXACT), (match_offs, "match_offs", i64, n_scenes + 1, EXACT),
+            (count, "count", i32, n_scenes, EXACT), (cam_offs, "cam_offs", i64, n_cams * n_scenes + 1, EXACT),
+            (used, "used", i32, None, ANY)]
+    if orig is not None:
+        rows += [(sub_cam_offs, "sub_cam_offs", i64, n_cams * n_scenes + 1, EXACT), (orig, "orig", i32, None, ANY)]
+    ops._check_args(dev, rows)
+    if n_scenes == 0 or cap == 0 or used.numel() == 0 or (orig is not None and orig.numel() == 0):
+        return                       # no row, or no detection a row could hold
+    ops._call("mvm_mark_used", ops._p(views), ops._p(match_offs), ops._p(count), cap, n_scenes, n_cams,
+              *seed, ops._p(sub_cam_offs), ops._p(orig), ops._p(cam_offs), used.numel(), ops._p(used),
+              ops._stream(views))
+
+
+@ops._gpu_op("leftover_counts_out", ("counts",), namespace="mvmatch_views")
+def leftover_counts_out(used: Tensor, cam_offs: Tensor, n_cams: int, seed: List[int], counts: Tensor) -> None:
+    """The unused detections per (capture, slot) of the seed's camera order
+    (mvm_leftover_counts)."""
+    dev = ops._gpu(cam_offs, "cam_offs", "leftover count")
+    seed = _check_seed(seed, n_cams)
+    n_views = cam_offs.numel() - 1
+    if n_views < 0 or n_views % n_cams:
+        raise ValueError(f"cam_offs must describe {n_cams} views per capture")
+    ops._check_args(dev, [(used, "used", i32, None, ANY), (cam_offs, "cam_offs", i64, n_views + 1, EXACT),
+                          (counts, "counts", i32, n_views, EXACT)])
+    if n_views == 0:
+        return
+    if used.numel() == 0:            # every view is empty: nothing to read
+        counts.zero_()
+        return
+    ops._call("mvm_leftover_counts", ops._p(used), ops._p(cam_offs), n_views // n_cams, n_cams, *seed,
+              ops._p(counts), ops._stream(cam_offs))
+
+
+@ops._gpu_op("leftover_gather_out", ("pts_out", "boxes_out", "orig_out"), namespace="mvmatch_views")
+def leftover_gather_out(used: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tensor, sub_cam_offs: Tensor,
+                        n_cams: int, seed: List[int], pts_out: Tensor, boxes_out: Tensor,
+                        orig_out: Tensor) -> None:
+    """The unused detections, compacted per view in the seed's camera order
+    (mvm_leftover_gather)."""
+    dev = ops._gpu(used, "used", "leftover gather")
+    seed = _check_seed(seed, n_cams)
+    n_views = cam_offs.numel() - 1
+    if n_views < 0 or n_views % n_cams:
+        raise ValueError(f"cam_offs must describe {n_cams} views per capture")
+    n, m = used.numel(), orig_out.numel()
+    ops._check_args(dev, [(used, "used", i32, None, ANY), (pts, "pts", f64, 2 * n, EXACT),
+                          (boxes, "boxes", i32, 4 * n, EXACT), (cam_offs, "cam_offs", i64, n_views + 1, EXACT),
+                          (sub_cam_offs, "sub_cam_offs", i64, n_views + 1, EXACT),
+                          (pts_out, "pts_out", f64, 2 * m, EXACT), (boxes_out, "boxes_out", i32, 4 * m, EXACT),
+                          (orig_out, "orig_out", i32, None, ANY)])
+    if n_views == 0 or n == 0 or m == 0:
+        return                       # nothing left over: nothing to launch
+    ops._call("mvm_leftover_gather", ops._p(used), ops._p(pts), ops._p(boxes), ops._p(cam_offs),
+              ops._p(sub_cam_offs), n_views // n_cams, n_cams, *seed, ops._p(pts_out), ops._p(boxes_out),
+              ops._p(orig_out), ops._stream(used))
+
+
+def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
+              seed=(0, 1, 2), sub_cam_offs: Optional[Tensor] = None, orig: Optional[Tensor] = None) -> Tensor:
+    """Flag the detections the matches of one pass hold (device).
+    ``views`` int32 [cap, n_cams] with capture s's matches at rows
+    ``match_offs[s] : match_offs[s] + count[s]``; ``used`` int32, one flag per
+    detection of the n_cams-camera CSR ``cam_offs`` (original camera order),
+    zeroed by the caller once and marked pass after pass.  A first pass passes
+    its views as they are; a later one its ``seed`` and its sub-batch's
+    ``sub_cam_offs`` / ``orig``, through which its views name original
+    detections.  Entries that are negative or no index of their view mark
+    nothing.  -> ``used``."""
+    torch.ops.mvmatch_views.mark_used_out(views, match_offs, count, int(n_cams), list(seed), sub_cam_offs,
+                                          orig, cam_offs, used)
+    return used
+
+
+def leftover_counts(used: Tensor, cam_offs: Tensor, n_cams: int, seed, out: Optional[Tensor] = None) -> Tensor:
+    """-> int32 [C S]: the detections with ``used == 0`` per (capture, slot),
+    slot q standing for camera ``seed_order(seed, n_cams)[q]`` (device)."""
+    if out is None:
+        out = torch.empty(max(int(cam_offs.numel()) - 1, 0), dtype=torch.int32, device=cam_offs.device)
+    torch.ops.mvmatch_views.leftover_counts_out(used, cam_offs, int(n_cams), list(seed), out)
+    return out
+
+
+def leftover_gather(used: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tensor, sub_cam_offs: Tensor,
+                    n_cams: int, seed, n_out: int):
+    """The sub-batch of a seed pass (device): the ``n_out`` unused detections
+    of ``pts`` f64 [n, 2] / ``boxes`` int32 [n, 4], per view in ascending
+    index order, views in the seed's camera order; ``sub_cam_offs`` int64
+    [C S + 1]: the prefix sum of ``leftover_counts``.
+    -> (pts f64 [n_out, 2], boxes int32 [n_out, 4], orig int32 [n_out]: each
+    one's index in its original view)."""
+    dev = used.device
+    outs = (torch.empty((n_out, 2), dtype=torch.float64, device=dev),
+            torch.empty((n_out, 4), dtype=torch.int32, device=dev),
+            torch.empty(n_out, dtype=torch.int32, device=dev))
+    torch.ops.mvmatch_views.leftover_gather_out(used, pts, boxes, cam_offs, sub_cam_offs, int(n_cams),
+                                                list(seed), *outs)
+    return outs
 
 
 def prune_views(views: Tensor, ext_cost: Tensor, X: Tensor, match_offs: Tensor, count: Tensor,

@@ -48,6 +48,8 @@ extern "C" {
                                 signature or struct changed) */
 #define MVM_HAS_VIEW_PRUNE 1 /* mvm_prune_views_triangulate: an addition to ABI 8 (no existing
                                 signature or struct changed) */
+#define MVM_HAS_LEFTOVERS 1 /* mvm_mark_used, mvm_leftover_counts, mvm_leftover_gather: additions
+                               to ABI 8 (no existing signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -709,6 +711,54 @@ int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *co
                                 const int64_t *cam_offs_dev, const double *proj_dev, double gate,
                                 int32_t *views_dev, float *ext_cost_dev, double *X_dev,
                                 int32_t *pruned_dev, mvm_stream_t stream);
+
+/*
+ * The leftovers of a C-camera batch, 4 <= C <= MVM_MAX_CAMS: what an extra
+ * seed pass is run on (additions to ABI 8, announced by MVM_HAS_LEFTOVERS).
+ * Every function takes the pass's seed triple (seed_a, seed_b, seed_c), three
+ * distinct cameras < C, which fixes the camera order pi = (seed_a, seed_b,
+ * seed_c, then the other cameras ascending): slot q stands for camera pi[q].
+ * cam_offs_dev int64 [C S + 1] is the batch's C-camera CSR in original camera
+ * order, used_dev int32 [n_det] a flag per detection of it.
+ *
+ * mvm_mark_used: for every match row w < count_dev[s] of capture s (rows
+ * match_offs_dev[s] + w of views_dev int32 [n_rows, C]; never more rows than
+ * match_offs[s+1] - match_offs[s]) and every slot q, the detection
+ * l = views[w][q] of camera pi[q] gets used_dev[cam_offs[s C + pi[q]] + l] = 1.
+ * With sub_cam_offs_dev (int64 [C S + 1], slot order) and orig_dev (int32, one
+ * per detection of that CSR) -- both or neither -- l indexes slot q's view of
+ * that CSR and orig_dev[sub_cam_offs[s C + q] + l] is the index in the original
+ * view: the result of an earlier extra pass.  An l that is negative or not an
+ * index of its view marks nothing; no other word of used_dev is written, so
+ * the caller zeroes it once and marks pass after pass.  The triple (0, 1, 2)
+ * is the identity order of a first pass.
+ *
+ * mvm_leftover_counts: counts_dev int32 [C S], slot order: counts[s C + q] =
+ * the detections of camera pi[q] of capture s whose flag is 0.
+ *
+ * mvm_leftover_gather: those detections, in ascending index order, to rows
+ * sub_cam_offs_dev[s C + q] + 0, 1, ... of pts_out_dev (f64 [.., 2]),
+ * boxes_out_dev (int32 [.., 4]) and orig_out_dev (int32: the index in the
+ * original view); sub_cam_offs_dev is the prefix sum of mvm_leftover_counts'
+ * result, and never more rows are written than it leaves a view.
+ *
+ * One launch each on `stream`; no allocation, copy or synchronisation.
+ * n_scenes == 0 launches nothing (and mvm_mark_used none for n_rows == 0 or
+ * n_det == 0).  A NULL pointer, n_cams outside 4..MVM_MAX_CAMS, a triple with a
+ * repeated or out-of-range camera is refused before the launch.
+ */
+int mvm_mark_used(const int32_t *views_dev, const int64_t *match_offs_dev, const int32_t *count_dev,
+                  int64_t n_rows, int32_t n_scenes, int32_t n_cams, int32_t seed_a, int32_t seed_b,
+                  int32_t seed_c, const int64_t *sub_cam_offs_dev, const int32_t *orig_dev,
+                  const int64_t *cam_offs_dev, int64_t n_det, int32_t *used_dev, mvm_stream_t stream);
+int mvm_leftover_counts(const int32_t *used_dev, const int64_t *cam_offs_dev, int32_t n_scenes,
+                        int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
+                        int32_t *counts_dev, mvm_stream_t stream);
+int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const int32_t *boxes_dev,
+                        const int64_t *cam_offs_dev, const int64_t *sub_cam_offs_dev, int32_t n_scenes,
+                        int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
+                        double *pts_out_dev, int32_t *boxes_out_dev, int32_t *orig_out_dev,
+                        mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

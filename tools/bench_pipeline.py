@@ -11,6 +11,9 @@ of the same captures, the three-camera line the extension is measured against.
 --reproj-gate G (with --cams C > 3): match_captures(reproj_gate=G) (DESIGN
 §3.15); the stage "prune" and the number of matches that dropped a view are
 in the line.
+--extra-seeds a,b,c[;a,b,c...] (with --cams C > 3):
+match_captures(extra_seeds=[(a, b, c), ...]); the stages of
+every extra pass ("pass 1: ...") and the matches each pass adds are in the line.
 """
 import argparse
 import json
@@ -85,6 +88,8 @@ def main_wide(args):
         kw["n_cams"] = C
         if args.reproj_gate is not None:
             kw["reproj_gate"] = args.reproj_gate
+        if args.extra_seeds:
+            kw["extra_seeds"] = [tuple(int(c) for c in seed.split(",")) for seed in args.extra_seeds.split(";")]
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     inp = (t(boxes), t(conf), t(cls), t(offs), Ks, RTs)
     for _ in range(args.warmup):
@@ -109,6 +114,9 @@ def main_wide(args):
     if res.pruned is not None:
         out["prune_ms_synchronised"] = stages.get("prune")
         out["matches_that_dropped_a_view"] = int((res.pruned != 0).sum())
+    if res.passes:
+        out["config"]["extra_seeds"] = [list(seed) for seed in kw["extra_seeds"]]
+        out["matches_per_extra_pass"] = [int(p.count.sum()) for p in res.passes]
     if not args.first_three:
         v = res.views.cpu().numpy()
         keep = np.concatenate([np.arange(o, o + n) for o, n in zip(res.offs[:-1], res.count)]
@@ -126,6 +134,8 @@ def main():
                     help="with --cams C > 3: match cameras 0-2 of the same captures only")
     ap.add_argument("--reproj-gate", type=float, default=None,
                     help="with --cams C > 3: match_captures(reproj_gate=G), pixels (DESIGN §3.15)")
+    ap.add_argument("--extra-seeds", default=None, metavar="a,b,c[;a,b,c...]",
+                    help="with --cams C > 3: match_captures(extra_seeds=[(a, b, c), ...]) (DESIGN §3.16)")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
