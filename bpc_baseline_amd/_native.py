@@ -202,6 +202,10 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, _vp,            # used, pts, boxes, cam_offs, sub_cam_offs
         _i32, _i32, _i32, _i32, _i32,       # n_scenes, n_cams, seed_a, seed_b, seed_c
         _vp, _vp, _vp, _vp]),               # pts, boxes, orig (out), stream
+    "mvm_refine_points": (ctypes.c_int, [
+        _vp, _vp, _i32, _i32,               # match_offs, count, n_scenes, n_cams
+        _vp, _vp, _vp, _vp, _vp, _i32,      # pts, cam_offs, proj, views, X, max_evals
+        _vp, _vp, _vp, _vp, _vp]),          # X_out, rms, info, cov (may be NULL) (out), stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -20,6 +20,8 @@
 //  * mvm_mark_used, mvm_leftover_counts, mvm_leftover_gather: the sub-batch of
 //    an extra seed pass over a C-camera batch: the detections no
 //    earlier match holds, compacted per view in order, cameras reordered.
+//  * mvm_refine_points: the minimiser of the summed squared reprojection
+//    error from the DLT point, with its covariance.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -706,6 +708,220 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
     }
 }
 
+// --------------------------------------------- point refinement ----
+// mvm_refine_points: per match, a damped Gauss-Newton descent
+// of the summed squared reprojection error from the DLT point, and the inverse
+// of the normal matrix at the result.  The shape of prune_views_kernel: one
+// wave per capture (its index a scalar, so the capture's P is read through
+// uniform addresses), four captures per workgroup, lanes striding over the
+// capture's matches; no LDS, no barrier.  The kept set is a bit mask and the
+// view loop runs over compile-time camera slots under the mask's bit, so no
+// register array is indexed by a runtime value.  Every product, sum, division
+// and square root is rounded on its own (this file's fp contract(off)), in
+// the order of tests/refine_model.py, whose bits the kernel returns.
+struct RefineSums {
+    double cost, A[6], g[3];     // A: A00 A01 A02 A11 A12 A22
+};
+
+__device__ __forceinline__ bool refine_finite(double x) { return __builtin_fabs(x) < INFINITY; }
+
+// cost, A and g at X over the views of `mask`, ascending
+__device__ __forceinline__ void refine_sums(const double *proj_s, uint32_t mask,
+                                            const double (&cx)[MVM_MAX_CAMS],
+                                            const double (&cy)[MVM_MAX_CAMS], double X0, double X1,
+                                            double X2, RefineSums &e) {
+    e.cost = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) e.A[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) e.g[q] = 0.0;
+#pragma unroll
+    for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+        if ((mask >> c) & 1u) {
+            const double *p = proj_s + 12 * c;
+            const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
+            const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
+            const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
+            const double u = h0 / h2, v = h1 / h2;
+            const double ru = u - cx[c], rv = v - cy[c];
+            e.cost = e.cost + (ru * ru + rv * rv);
+            const double a0 = (p[0] - u * p[8]) / h2, a1 = (p[1] - u * p[9]) / h2,
+                         a2 = (p[2] - u * p[10]) / h2;
+            const double b0 = (p[4] - v * p[8]) / h2, b1 = (p[5] - v * p[9]) / h2,
+                         b2 = (p[6] - v * p[10]) / h2;
+            e.A[0] = e.A[0] + (a0 * a0 + b0 * b0);
+            e.A[1] = e.A[1] + (a0 * a1 + b0 * b1);
+            e.A[2] = e.A[2] + (a0 * a2 + b0 * b2);
+            e.A[3] = e.A[3] + (a1 * a1 + b1 * b1);
+            e.A[4] = e.A[4] + (a1 * a2 + b1 * b2);
+            e.A[5] = e.A[5] + (a2 * a2 + b2 * b2);
+            e.g[0] = e.g[0] + (a0 * ru + b0 * rv);
+            e.g[1] = e.g[1] + (a1 * ru + b1 * rv);
+            e.g[2] = e.g[2] + (a2 * ru + b2 * rv);
+        }
+    }
+}
+
+// M = L D L^T of the symmetric M (upper triangle, row-major) in the model's
+// order -> every pivot > 0 (a NaN is not); the factors mean nothing otherwise
+struct RefineLdlt {
+    double d0, d1, d2, l10, l20, l21;
+};
+
+__device__ __forceinline__ bool refine_ldlt(double M00, double M01, double M02, double M11,
+                                            double M12, double M22, RefineLdlt &f) {
+    f.d0 = M00;
+    f.l10 = M01 / f.d0;
+    f.l20 = M02 / f.d0;
+    f.d1 = M11 - f.l10 * M01;
+    const double t = M12 - f.l20 * M01;
+    f.l21 = t / f.d1;
+    f.d2 = (M22 - f.l20 * M02) - f.l21 * t;
+    return f.d0 > 0.0 && f.d1 > 0.0 && f.d2 > 0.0;
+}
+
+__global__ __launch_bounds__(kCompactThreads) void refine_points_kernel(
+    const int64_t *__restrict__ match_offs, const int32_t *__restrict__ count,
+    const double *__restrict__ pts, const int64_t *__restrict__ cam_offs,
+    const double *__restrict__ proj, const int32_t *__restrict__ views, const double *__restrict__ X,
+    int32_t n_scenes, int32_t n_cams, int32_t max_evals, double *__restrict__ X_out,
+    double *__restrict__ rms, int32_t *__restrict__ info, double *__restrict__ cov) {
+    const int lane = threadIdx.x % 64;
+    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
+                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    if (s >= n_scenes) return;
+    const int64_t mo = match_offs[s];
+    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
+    const int64_t *co_s = cam_offs + s * n_cams;     // cam_offs holds C S + 1 entries
+    const double *proj_s = proj + s * n_cams * 12;
+    const double qnan = __builtin_nan("");
+    for (int64_t w = lane; w < n; w += 64) {
+        const int64_t row = mo + w;
+        const double Xi0 = X[3 * row], Xi1 = X[3 * row + 1], Xi2 = X[3 * row + 2];
+        // the kept views; an entry that is no detection of its view skips the
+        // row: no index is used unchecked
+        uint32_t mask = 0u;
+        bool ok = true;
+        double cx[MVM_MAX_CAMS], cy[MVM_MAX_CAMS];
+#pragma unroll
+        for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+            if (c < n_cams) {
+                const int32_t v = views[row * n_cams + c];
+                if (v >= 0) {
+                    if (v < co_s[c + 1] - co_s[c]) {
+                        mask |= 1u << c;
+                        cx[c] = pts[2 * (co_s[c] + v)];
+                        cy[c] = pts[2 * (co_s[c] + v) + 1];
+                    } else {
+                        ok = false;
+                    }
+                }
+            }
+        }
+        const int kept = __builtin_popcount(mask);
+        double X0 = Xi0, X1 = Xi1, X2 = Xi2, rms0 = qnan, rms1 = qnan;
+        int32_t status = 3, evals = 0;
+        RefineSums cur;
+        if (ok && kept >= 2) {
+            refine_sums(proj_s, mask, cx, cy, X0, X1, X2, cur);
+            const double cost0 = cur.cost;
+            double A_in[6];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) A_in[q] = cur.A[q];
+            double cost = cost0, lam = 1e-3;
+            bool sums_ok = refine_finite(cost);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) sums_ok &= refine_finite(cur.A[q]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) sums_ok &= refine_finite(cur.g[q]);
+            status = sums_ok ? -1 : 2;
+            while (status < 0) {
+                RefineLdlt f;
+                const bool pivots = refine_ldlt(cur.A[0] + lam * cur.A[0], cur.A[1], cur.A[2],
+                                                cur.A[3] + lam * cur.A[3], cur.A[4],
+                                                cur.A[5] + lam * cur.A[5], f);
+                const double y0 = -cur.g[0];
+                const double y1 = -cur.g[1] - f.l10 * y0;
+                const double y2 = (-cur.g[2] - f.l20 * y0) - f.l21 * y1;
+                const double z0 = y0 / f.d0, z1 = y1 / f.d1, z2 = y2 / f.d2;
+                const double e2 = z2;
+                const double e1 = z1 - f.l21 * e2;
+                const double e0 = (z0 - f.l10 * e1) - f.l20 * e2;
+                if (!pivots || !(refine_finite(e0) && refine_finite(e1) && refine_finite(e2))) {
+                    status = 2;
+                    break;
+                }
+                if ((e0 * e0 + e1 * e1) + e2 * e2 <= 1e-20 * ((X0 * X0 + X1 * X1) + X2 * X2)) {
+                    status = 0;
+                    break;
+                }
+                if (evals == max_evals) {
+                    status = 1;
+                    break;
+                }
+                ++evals;
+                const double Y0 = X0 + e0, Y1 = X1 + e1, Y2 = X2 + e2;
+                RefineSums tr;
+                refine_sums(proj_s, mask, cx, cy, Y0, Y1, Y2, tr);
+                if (tr.cost < cost) {                // a NaN fails this
+                    X0 = Y0, X1 = Y1, X2 = Y2;
+                    cost = tr.cost;
+                    cur = tr;
+                    lam = fmax(lam / 10.0, 1e-15);
+                    bool finite = true;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) finite &= refine_finite(cur.A[q]);
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) finite &= refine_finite(cur.g[q]);
+                    if (!finite) status = 2;
+                } else {
+                    lam = lam * 10.0;
+                }
+            }
+            if (status == 2) {                       // the input stands
+                X0 = Xi0, X1 = Xi1, X2 = Xi2;
+                cost = cost0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) cur.A[q] = A_in[q];
+            }
+            const double k = (double)kept;
+            rms0 = sqrt(cost0 / k);
+            rms1 = sqrt(cost / k);
+        }
+        X_out[3 * row] = X0;
+        X_out[3 * row + 1] = X1;
+        X_out[3 * row + 2] = X2;
+        rms[2 * row] = rms0;
+        rms[2 * row + 1] = rms1;
+        info[2 * row] = status;
+        info[2 * row + 1] = evals;
+        if (cov != nullptr) {
+            double c00 = qnan, c01 = qnan, c02 = qnan, c11 = qnan, c12 = qnan, c22 = qnan;
+            if (status != 3) {
+                // A^-1 = L^-T D^-1 L^-1 of the undamped A at X_out
+                RefineLdlt f;
+                if (refine_ldlt(cur.A[0], cur.A[1], cur.A[2], cur.A[3], cur.A[4], cur.A[5], f)) {
+                    const double i0 = 1.0 / f.d0, i1 = 1.0 / f.d1, i2 = 1.0 / f.d2;
+                    const double m20 = f.l10 * f.l21 - f.l20;
+                    const double q2 = f.l21 * i2, p1 = f.l10 * i1, r2 = m20 * i2;
+                    c00 = (i0 + f.l10 * p1) + m20 * r2;
+                    c01 = -p1 - m20 * q2;
+                    c02 = r2;
+                    c11 = i1 + f.l21 * q2;
+                    c12 = -q2;
+                    c22 = i2;
+                }
+            }
+            cov[6 * row] = c00;
+            cov[6 * row + 1] = c01;
+            cov[6 * row + 2] = c02;
+            cov[6 * row + 3] = c11;
+            cov[6 * row + 4] = c12;
+            cov[6 * row + 5] = c22;
+        }
+    }
+}
+
 // ------------------------------------------------- rig matrices ----
 // compute_fundamental_matrix (camera_utils.py:23-46) for every (capture, pair)
 // and P = K @ RT[:3] (process_pose.py:91) for every (capture, camera): one
@@ -1135,6 +1351,31 @@ int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *co
         match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, gate, n_scenes, n_cams, views_dev,
         ext_cost_dev, X_dev, pruned_dev);
     return mvm_check_launch("prune_views_kernel");
+}
+
+int mvm_refine_points(const int64_t *match_offs_dev, const int32_t *count_dev, int32_t n_scenes,
+                      int32_t n_cams, const double *pts_dev, const int64_t *cam_offs_dev,
+                      const double *proj_dev, const int32_t *views_dev, const double *X_dev,
+                      int32_t max_evals, double *X_out_dev, double *rms_dev, int32_t *info_dev,
+                      double *cov_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
+    if (n_scenes == 0) return MVM_OK;
+    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    if (max_evals < 1 || max_evals > 64)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "max_evals=%d outside [1, 64]", max_evals);
+    if (const int st = mvm_require_ptrs({{match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
+                                         {pts_dev, "pts_dev"},               {cam_offs_dev, "cam_offs_dev"},
+                                         {proj_dev, "proj_dev"},             {views_dev, "views_dev"},
+                                         {X_dev, "X_dev"},                   {X_out_dev, "X_out_dev"},
+                                         {rms_dev, "rms_dev"},               {info_dev, "info_dev"}}))
+        return st;                       // cov_dev may be NULL: no covariance is written
+    const int grid = (int)(((int64_t)n_scenes + kCompactScenes - 1) / kCompactScenes);
+    refine_points_kernel<<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+        match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, views_dev, X_dev, n_scenes, n_cams,
+        max_evals, X_out_dev, rms_dev, info_dev, cov_dev);
+    return mvm_check_launch("refine_points_kernel");
 }
 
 int mvm_mark_used(const int32_t *views_dev, const int64_t *match_offs_dev, const int32_t *count_dev,

@@ -144,13 +144,24 @@ class MatchBatch:
     cam_order: Optional[tuple] = None
     orig: Optional[torch.Tensor] = None           # int32 [n]
     passes: tuple = ()
+    # match_captures(refine=...): X then holds the points
+    # refined by reprojection error and these the DLT points they started
+    # from, sqrt(cost / views) before and after in pixels, (status,
+    # evaluations) and the upper triangle of the inverse normal matrix at X
+    # (mm^2 / px^2; times the pixel variance: the covariance).  All None
+    # without the keyword
+    X_dlt: Optional[torch.Tensor] = None          # float64 [cap, 3]
+    refine_rms: Optional[torch.Tensor] = None     # float64 [cap, 2]
+    refine_info: Optional[torch.Tensor] = None    # int32 [cap, 2]
+    cov: Optional[torch.Tensor] = None            # float64 [cap, 6]
 
     def host(self) -> dict:
         """One D2H copy of everything ``predictions`` reads (and ``pruned``
-        when the batch has it)."""
+        and the refinement's fields when the batch has them)."""
         if not hasattr(self, "_host"):
             keys = ("match", "cost", "X", "pts", "boxes") + (("views",) if self.n_cams > 3 else ())
             keys += ("pruned",) if self.pruned is not None else ()
+            keys += tuple(k for k in ("X_dlt", "refine_rms", "refine_info", "cov") if getattr(self, k) is not None)
             self._host = {k: getattr(self, k).cpu().numpy() for k in keys}
         return self._host
 
@@ -377,7 +388,7 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    F: Optional[torch.Tensor] = None,
                    proj: Optional[torch.Tensor] = None, rig: str = "host",
                    n_cams: int = 3, reproj_gate: Optional[float] = None,
-                   extra_seeds: Optional[Sequence] = None) -> MatchBatch:
+                   extra_seeds: Optional[Sequence] = None, refine=None) -> MatchBatch:
     """Detect-packing + matching + triangulation of S 3-camera captures.
 
     ``boxes`` f32 [n, 4] xyxy, ``conf``/``cls`` f32 [n]: the detector outputs
@@ -446,8 +457,24 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
     camera order.  ``ValueError`` for a bad triple or ``n_cams=3``;
     ``TypeError`` with ``F`` / ``proj``, since a pass needs the F and P of
     its own pair list.
+
+    ``refine`` (None, the default: off, nothing launched, today's result;
+    True: at most 10 evaluations; an int 1..64: that many): at the end of
+    every pass -- behind the extension and the gate, so over the views the gate
+    left --, every match's X is refined from its DLT point by minimising the
+    summed squared reprojection error over its views (``n_cams=3``: the three
+    of them), by damped Gauss-Newton steps that never raise it
+    (``ops_views.refine_points``; on the device, no further
+    device -> host copy).  ``X`` then holds the refined points, so tables and
+    ``predictions`` carry them; ``X_dlt`` the DLT points, ``refine_rms`` the
+    rms reprojection error before and after, ``refine_info`` (status,
+    evaluations) and ``cov`` the inverse normal matrix at X, whose product
+    with the pixel variance is the point's covariance.  Every other field is
+    byte for byte that of the call without the keyword.  ``ValueError`` for
+    anything else.
     """
     C = _check_n_cams(n_cams)
+    refine = _check_refine(refine)
     _check_rig(rig)
     gate = None if reproj_gate is None else ops_views._check_gate(reproj_gate)
     if rig != "host" and (F is not None or proj is not None):
@@ -506,10 +533,21 @@ def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
 
     threshold = float(matching_threshold)
     full = _Rig(pts, cam_offs, cam_offs_host, counts_host.reshape(S, C), F_dev, proj)
-    out = _match_rig(full, boxes_int, S, C, threshold, keep_cube, gate, mark)
+    out = _match_rig(full, boxes_int, S, C, threshold, keep_cube, gate, refine, mark)
     if seeds:
-        out.passes = _seed_passes(out, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, mark)
+        out.passes = _seed_passes(out, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, refine, mark)
     return out
+
+
+def _check_refine(refine) -> Optional[int]:
+    """``match_captures``' refine as the cap of the evaluations (None: off)."""
+    if refine is None:
+        return None
+    if refine is True:
+        return 10
+    if isinstance(refine, (int, np.integer)) and not isinstance(refine, bool) and 1 <= refine <= 64:
+        return int(refine)
+    raise ValueError(f"refine: expected None, True or an int in 1..64, got {refine!r}")
 
 
 def _check_extra_seeds(extra_seeds, C: int) -> tuple:
@@ -560,7 +598,8 @@ def _rig_fallback(F, proj, rig_bad, Ks, RTs, S, C, on_device, dev) -> None:
         proj.index_copy_(0, idx, torch.from_numpy(P_h).to(dev))
 
 
-def _seed_passes(first: MatchBatch, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, mark) -> tuple:
+def _seed_passes(first: MatchBatch, seeds, Ks, RTs, rig, on_device, S, C, threshold, gate, refine,
+                 mark) -> tuple:
     """The extra seed passes behind the first: per triple the
     leftovers of every view as a sub-batch in the triple's camera order, F and
     P of the reordered rig by the call's ``rig`` path, and ``_match_rig`` on
@@ -595,7 +634,8 @@ def _seed_passes(first: MatchBatch, seeds, Ks, RTs, rig, on_device, S, C, thresh
                                                      C, seed, int(sub_offs[-1]))
         mark_p("leftover gather")
         sub = _Rig(pts, sub_offs_dev, sub_offs, sub_counts.reshape(S, C), F.reshape(-1), proj)
-        res = _match_rig(sub, boxes, S, C, threshold, False, gate, mark_p, cam_order=order, orig=orig)
+        res = _match_rig(sub, boxes, S, C, threshold, False, gate, refine, mark_p, cam_order=order,
+                         orig=orig)
         passes.append(res)
         if p < len(seeds):
             ops_views.mark_used(res.views, res.offs_dev, res.count_dev, full_offs, used, C, seed,
@@ -604,10 +644,10 @@ def _seed_passes(first: MatchBatch, seeds, Ks, RTs, rig, on_device, S, C, thresh
     return tuple(passes)
 
 
-def _match_rig(full: _Rig, boxes_int, S, C, threshold, keep_cube, gate, mark, **fields) -> MatchBatch:
+def _match_rig(full: _Rig, boxes_int, S, C, threshold, keep_cube, gate, refine, mark, **fields) -> MatchBatch:
     """What follows the count copy: the three-camera chain on the first three
-    views of ``full``, the extension into the others, the gate if set ->
-    the ``MatchBatch`` (``fields``: further fields of it)."""
+    views of ``full``, the extension into the others, the gate and the
+    refinement if set -> the ``MatchBatch`` (``fields``: further fields of it)."""
     pts = full.pts
     dev = pts.device
     counts_host = full.counts.reshape(-1)
@@ -649,7 +689,14 @@ def _match_rig(full: _Rig, boxes_int, S, C, threshold, keep_cube, gate, mark, **
             ops_views.prune_views(views, ext_cost, res.X, res.offs_dev, res.count, full.pts, full.cam_offs,
                                   full.proj, gate, C, out=pruned)
             mark("prune")
-    return MatchBatch(match=res.match, cost=res.cost, X=res.X, count=count_h, offs=res.offs_host,
+    X = res.X
+    if refine is not None:
+        # over the views the gate left; the DLT points stay as X_dlt
+        X, rms, info, cov = ops_views.refine_points(views if C > 3 else res.match, res.X, res.offs_dev,
+                                                    res.count, full.pts, full.cam_offs, full.proj, C, refine)
+        fields.update(X_dlt=res.X, refine_rms=rms, refine_info=info, cov=cov)
+        mark("refine")
+    return MatchBatch(match=res.match, cost=res.cost, X=X, count=count_h, offs=res.offs_host,
                       pts=full.pts, boxes=boxes_int, cam_offs=full.cam_offs_host,
                       cube=res.cube if keep_cube else None, offs_dev=res.offs_dev, count_dev=res.count,
                       cam_offs_dev=full.cam_offs, views=views, ext_cost=ext_cost, n_cams=C,
@@ -842,7 +889,7 @@ def match_capture_stream(batches: Iterable[Sequence], *, rig_workers: int = 3, r
     ``n_cams`` (in ``kwargs``) is passed through; the worker processes compute
     three-camera rigs, so a stream of n_cams > 3 computes F / P inline.
     ``extra_seeds`` is passed through as well (it needs n_cams > 3, so that
-    inline path).
+    inline path), and so is ``refine``.
     """
     if "F" in kwargs or "proj" in kwargs:
         raise TypeError("match_capture_stream computes F and proj itself")

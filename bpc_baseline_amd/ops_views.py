@@ -11,6 +11,7 @@ fake that returns None.
   mvmatch_views::mark_used_out         mvm_mark_used               (DESIGN §3.16)
   mvmatch_views::leftover_counts_out   mvm_leftover_counts
   mvmatch_views::leftover_gather_out   mvm_leftover_gather
+  mvmatch_views::refine_points_out     mvm_refine_points           (DESIGN §3.17)
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from torch import Tensor
 from . import _native, ops
 from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64
 
-__all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather"]
+__all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points"]
 
 
 def _check_gate(gate) -> float:
@@ -151,6 +152,43 @@ def leftover_gather_out(used: Tensor, pts: Tensor, boxes: Tensor, cam_offs: Tens
               ops._p(orig_out), ops._stream(used))
 
 
+def _check_max_evals(max_evals) -> int:
+    if isinstance(max_evals, bool) or not isinstance(max_evals, int) or not 1 <= max_evals <= 64:
+        raise ValueError(f"max_evals: expected an int in 1..64, got {max_evals!r}")
+    return max_evals
+
+
+@ops._gpu_op("refine_points_out", ("X_out", "rms", "info", "cov"), namespace="mvmatch_views")
+def refine_points_out(views: Tensor, X: Tensor, match_offs: Tensor, count: Tensor, pts: Tensor,
+                      cam_offs: Tensor, proj: Tensor, n_cams: int, max_evals: int, X_out: Tensor,
+                      rms: Tensor, info: Tensor, cov: Optional[Tensor]) -> None:
+    """Refine every match's point by its reprojection error and give its
+    covariance (mvm_refine_points).  ``views`` / ``X`` are read only; ``X_out``
+    / ``rms`` / ``info`` / ``cov`` (None: not computed) out."""
+    dev = ops._gpu(views, "views", "point refinement")
+    if not 3 <= n_cams <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if views.dim() != 2 or views.shape[1] != n_cams:
+        raise ValueError(f"views must be [cap, {n_cams}]")
+    max_evals = _check_max_evals(max_evals)
+    cap, n_scenes = int(views.shape[0]), count.numel()
+    rows = [(views, "views", i32, n_cams * cap, AT_LEAST), (X, "X", f64, 3 * cap, AT_LEAST),
+            (match_offs, "match_offs", i64, n_scenes + 1, EXACT), (count, "count", i32, n_scenes, EXACT),
+            (pts, "pts", f64, None, ANY), (cam_offs, "cam_offs", i64, n_cams * n_scenes + 1, EXACT),
+            (proj, "proj", f64, 12 * n_cams * n_scenes, EXACT), (X_out, "X_out", f64, 3 * cap, AT_LEAST),
+            (rms, "rms", f64, 2 * cap, AT_LEAST), (info, "info", i32, 2 * cap, AT_LEAST)]
+    if cov is not None:
+        rows.append((cov, "cov", f64, 6 * cap, AT_LEAST))
+    ops._check_args(dev, rows)
+    if X_out.data_ptr() == X.data_ptr() and cap:
+        raise ValueError("X_out must not be X: the input is kept")
+    if n_scenes == 0 or cap == 0 or pts.numel() == 0:
+        return                       # no match a capture could hold: nothing to launch
+    ops._call("mvm_refine_points", ops._p(match_offs), ops._p(count), n_scenes, n_cams, ops._p(pts),
+              ops._p(cam_offs), ops._p(proj), ops._p(views), ops._p(X), max_evals, ops._p(X_out),
+              ops._p(rms), ops._p(info), ops._p(cov), ops._stream(views))
+
+
 def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
               seed=(0, 1, 2), sub_cam_offs: Optional[Tensor] = None, orig: Optional[Tensor] = None) -> Tensor:
     """Flag the detections the matches of one pass hold (device).
@@ -215,3 +253,33 @@ def prune_views(views: Tensor, ext_cost: Tensor, X: Tensor, match_offs: Tensor, 
     torch.ops.mvmatch_views.prune_views_out(views, ext_cost, X, match_offs, count, pts, cam_offs,
                                             proj.contiguous(), float(gate), int(n_cams), out)
     return out
+
+
+def refine_points(views: Tensor, X: Tensor, match_offs: Tensor, count: Tensor, pts: Tensor,
+                  cam_offs: Tensor, proj: Tensor, n_cams: int, max_evals: int = 10, cov: bool = True):
+    """Refine triangulated points by their reprojection error (device; DESIGN
+    §3.17).  ``views`` int32 [cap, n_cams] (a three-camera batch: its
+    ``match``) and ``X`` f64 [cap, 3] as the chain left them, neither written;
+    ``match_offs`` / ``count`` / ``pts`` / ``cam_offs`` / ``proj`` as
+    ``prune_views`` takes them.  Per match, over the views with ``views >= 0``:
+    the summed squared reprojection error is minimised from X by damped
+    Gauss-Newton steps that never raise it, at most ``max_evals`` (1..64)
+    trial evaluations.
+    -> (X_out f64 [cap, 3]; rms f64 [cap, 2]: sqrt(cost / views) at X and at
+    X_out, pixels; info int32 [cap, 2]: (status, evaluations), status 0
+    converged, 1 stopped at ``max_evals``, 2 not finite or singular (X_out =
+    X), 3 skipped: fewer than two views or an index outside its view (X_out =
+    X, rms / cov NaN); cov f64 [cap, 6] or None with ``cov=False``: the upper
+    triangle, row-major, of the inverse normal matrix at X_out, mm^2 / px^2 --
+    times the pixel variance, the point's covariance).  Only the captures'
+    match rows are written; the others hold NaN / (3, 0)."""
+    max_evals = _check_max_evals(max_evals)       # before the op's schema turns a bool or a float into an int
+    cap, dev = int(views.shape[0]), views.device
+    X_out = torch.full((cap, 3), math.nan, dtype=torch.float64, device=dev)
+    rms = torch.full((cap, 2), math.nan, dtype=torch.float64, device=dev)
+    info = torch.zeros((cap, 2), dtype=torch.int32, device=dev)
+    info[:, 0] = 3
+    cv = torch.full((cap, 6), math.nan, dtype=torch.float64, device=dev) if cov else None
+    torch.ops.mvmatch_views.refine_points_out(views, X, match_offs, count, pts, cam_offs, proj.contiguous(),
+                                              int(n_cams), max_evals, X_out, rms, info, cv)
+    return X_out, rms, info, cv

@@ -50,6 +50,8 @@ extern "C" {
                                 signature or struct changed) */
 #define MVM_HAS_LEFTOVERS 1 /* mvm_mark_used, mvm_leftover_counts, mvm_leftover_gather: additions
                                to ABI 8 (no existing signature or struct changed) */
+#define MVM_HAS_REFINE 1 /* mvm_refine_points: an addition to ABI 8 (no existing signature or
+                            struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -759,6 +761,45 @@ int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const in
                         int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
                         double *pts_out_dev, int32_t *boxes_out_dev, int32_t *orig_out_dev,
                         mvm_stream_t stream);
+
+/*
+ * Refinement of triangulated points by reprojection error, with covariance,
+ * for a C-camera batch, 3 <= C <= MVM_MAX_CAMS (an addition to ABI 8,
+ * announced by MVM_HAS_REFINE).  Inputs, none written:
+ * views_dev int32 [.., C] (a three-camera batch passes its match array) and
+ * X_dev f64 [.., 3] with capture s's count_dev[s] matches at rows
+ * match_offs_dev[s] + w (never more rows than match_offs[s+1] - match_offs[s]);
+ * pts_dev / cam_offs_dev the C-camera CSR, proj_dev f64 [S, C, 3, 4].
+ * For match w the kept set is K = {d < C : views[w][d] >= 0}, ascending.  From
+ * X the summed squared reprojection error over K is minimised by damped
+ * Gauss-Newton steps: the normal matrix A and gradient g of the residuals
+ * (u - cx, v - cy), (A + lambda diag A) delta = -g solved by a 3 x 3 LDL^T,
+ * a step taken only where it lowers the cost (lambda / 10, floor 1e-15;
+ * else lambda * 10; lambda starts at 1e-3), until
+ * delta.delta <= 1e-20 X.X or max_evals (1..64) trial costs were evaluated.
+ * Every operation and its order are stated by tests/refine_model.py, whose
+ * bits the kernel returns.  Outputs per row:
+ *   X_out_dev f64 [.., 3]   the refined point (never a higher cost than X);
+ *   rms_dev   f64 [.., 2]   sqrt(cost / |K|) at X and at X_out, pixels;
+ *   info_dev  int32 [.., 2] (status, trial costs evaluated); status 0:
+ *             converged, 1: stopped at max_evals, 2: a non-finite cost, A, g or
+ *             delta, or a pivot that is not > 0 (X_out = X), 3: skipped, since
+ *             |K| < 2 or an entry of K is no detection of its view (X_out = X,
+ *             rms and cov NaN): no index is used unchecked;
+ *   cov_dev   f64 [.., 6]   may be NULL; the upper triangle, row-major, of the
+ *             inverse of the undamped A at X_out (mm^2 / px^2: times the
+ *             caller's pixel variance), NaN where a pivot is not > 0.
+ * Only the count_dev[s] rows of every capture are written.  X_out_dev must not
+ * overlap X_dev.  One launch on `stream`, a wave per capture; no allocation,
+ * copy or synchronisation.  n_scenes == 0 launches nothing.  A NULL pointer
+ * other than cov_dev, n_cams outside 3..MVM_MAX_CAMS or max_evals outside
+ * 1..64 is refused before the launch.
+ */
+int mvm_refine_points(const int64_t *match_offs_dev, const int32_t *count_dev, int32_t n_scenes,
+                      int32_t n_cams, const double *pts_dev, const int64_t *cam_offs_dev,
+                      const double *proj_dev, const int32_t *views_dev, const double *X_dev,
+                      int32_t max_evals, double *X_out_dev, double *rms_dev, int32_t *info_dev,
+                      double *cov_dev, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

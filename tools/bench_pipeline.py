@@ -14,6 +14,9 @@ in the line.
 --extra-seeds a,b,c[;a,b,c...] (with --cams C > 3):
 match_captures(extra_seeds=[(a, b, c), ...]); the stages of
 every extra pass ("pass 1: ...") and the matches each pass adds are in the line.
+--refine [N] (with --cams C > 3): match_captures(refine=True or N) (DESIGN
+§3.17); the stage "refine" and the distribution of the refinement's status and
+evaluations over the matches are in the line.
 """
 import argparse
 import json
@@ -90,6 +93,8 @@ def main_wide(args):
             kw["reproj_gate"] = args.reproj_gate
         if args.extra_seeds:
             kw["extra_seeds"] = [tuple(int(c) for c in seed.split(",")) for seed in args.extra_seeds.split(";")]
+        if args.refine is not None:
+            kw["refine"] = True if args.refine == 0 else args.refine
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     inp = (t(boxes), t(conf), t(cls), t(offs), Ks, RTs)
     for _ in range(args.warmup):
@@ -114,6 +119,14 @@ def main_wide(args):
     if res.pruned is not None:
         out["prune_ms_synchronised"] = stages.get("prune")
         out["matches_that_dropped_a_view"] = int((res.pruned != 0).sum())
+    if res.refine_info is not None:
+        keep = np.concatenate([np.arange(o, o + n) for o, n in zip(res.offs[:-1], res.count)]
+                              + [np.zeros(0, np.int64)]).astype(np.int64)
+        info = res.refine_info.cpu().numpy()[keep]
+        out["config"]["refine"] = kw["refine"]
+        out["refine_ms_synchronised"] = stages.get("refine")
+        out["refine_status_counts"] = np.bincount(info[:, 0], minlength=4).tolist()
+        out["refine_evals_counts"] = np.bincount(info[:, 1]).tolist()
     if res.passes:
         out["config"]["extra_seeds"] = [list(seed) for seed in kw["extra_seeds"]]
         out["matches_per_extra_pass"] = [int(p.count.sum()) for p in res.passes]
@@ -136,6 +149,8 @@ def main():
                     help="with --cams C > 3: match_captures(reproj_gate=G), pixels (DESIGN §3.15)")
     ap.add_argument("--extra-seeds", default=None, metavar="a,b,c[;a,b,c...]",
                     help="with --cams C > 3: match_captures(extra_seeds=[(a, b, c), ...]) (DESIGN §3.16)")
+    ap.add_argument("--refine", type=int, nargs="?", const=0, default=None, metavar="N",
+                    help="with --cams C > 3: match_captures(refine=True), or refine=N evaluations (DESIGN §3.17)")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -151,6 +166,8 @@ def main():
     args = ap.parse_args()
     if args.reproj_gate is not None and (args.cams == 3 or args.first_three):
         ap.error("--reproj-gate needs --cams C > 3 without --first-three (it acts on the extra views)")
+    if args.refine is not None and (args.cams == 3 or args.first_three):
+        ap.error("--refine needs --cams C > 3 without --first-three")
     if args.cams > 3:
         return main_wide(args)
     dev = torch.device("cuda", 0)
