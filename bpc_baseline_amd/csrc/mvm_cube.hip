@@ -938,7 +938,7 @@ void triplet_fused_kernel(CubeFusedArgs args) {
                     v[q] = (float)third_q((v12 + a13[q]) + a23[r][q]);   // (e12 + e13) + e23, :81
                 uint32_t off = (uint32_t)kb * 4u;
                 __asm__ volatile("" : "+v"(off));   // a 32-bit lane offset at the store: saddr form
-                store4_nt_row(p, off, v);
+                store4_row_a4<1>(p, off, v);   // cube_offs[s] may be any residue mod 4: dword-aligned rows
                 p += kRowBytes;
                 __asm__ volatile("" : "+s"(p));     // one running scalar row address
                 const uint32_t b0 = __float_as_uint(v[0]), b1 = __float_as_uint(v[1]);
@@ -1944,6 +1944,12 @@ int cube_launch(const double *pts_dev, const int64_t *cam_offs_dev, const double
         return mvm_fail(MVM_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, need);
     if (((uintptr_t)workspace_dev & 15) != 0)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "workspace not 16-byte aligned");
+    // the kernels pick 16-byte cube accesses and 8-byte key stores from the
+    // offsets alone (cube_offs[s] % 4, bmin8_offs[s] % 4): the bases carry the rest
+    if (((uintptr_t)cube_dev & 15) != 0)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cube not 16-byte aligned");
+    if (((uintptr_t)bmin8_dev & 7) != 0)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "bmin8 not 8-byte aligned");
     const int kernel = o.cube_kernel;
     const CubeIn in{pts_dev, cam_offs_dev, F_dev};
     const CubeOut out{cube_offs_dev, row_offs_dev, cube_dev, argmin_dev, minval_dev};

@@ -697,6 +697,14 @@ __global__ __launch_bounds__(kSpNT) __attribute__((amdgpu_waves_per_eu(KS == 1 ?
     const bool tr = Kd < R;
     const int S = (int)(tr ? Kd : R), L = (int)(tr ? R : Kd);
     const int cap = a.s_cap;
+    const SpLayout y = lsap_sparse_layout(S, L, sizeof(CT), tr, a.bm32 != nullptr);
+    // the counters of every problem of the class are defined after a solve: a
+    // problem that ends with a status other than 0 leaves them 0
+    if (threadIdx.x == 0) {
+        int32_t *stt = reinterpret_cast<int32_t *>(a.ws + a.ws_offs[p] + y.stats);
+#pragma unroll
+        for (int q = 0; q < kSpStats; ++q) stt[q] = 0;
+    }
     // the LDS was sized by the launch's bounds (short_max -> cap and the slots
     // per thread, long_max -> the bitmaps' lw words): a problem past them
     // would write out of range or drop slots; refuse it
@@ -706,7 +714,6 @@ __global__ __launch_bounds__(kSpNT) __attribute__((amdgpu_waves_per_eu(KS == 1 ?
         if (threadIdx.x == 0) a.status[p] = kSpStatusBounds;
         return;
     }
-    const SpLayout y = lsap_sparse_layout(S, L, sizeof(CT), tr, a.bm32 != nullptr);
     const unsigned char *ws = a.ws + a.ws_offs[p];
     const int32_t *lcol = reinterpret_cast<const int32_t *>(ws + y.lcol);
     const CT *lval = reinterpret_cast<const CT *>(ws + y.lval);

@@ -966,6 +966,10 @@ int mvm_pairwise_residual_argmin_pitched(const double *pts_dev, const int64_t *c
     if (n_scenes > 0 && max_n > 0 && (!pts_dev || !cam_offs_dev || !F_dev))
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null input pointer");
     if (dist_dev && !dist_offs_dev) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "dist without dist_offs");
+    // the kernels pick 16-byte row stores from dist_offs[s, p] % 4 and the
+    // pitch % 4 alone: the base carries the rest
+    if (((uintptr_t)dist_dev & 15) != 0)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "dist not 16-byte aligned");
     if ((argmin_dev || minval_dev) && !row_offs_dev)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "argmin/minval without row_offs");
     a.pts = pts_dev;
@@ -1020,6 +1024,9 @@ int mvm_pairwise_residual_f64(const double *pts_dev, const int64_t *cam_offs_dev
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
     if (ld <= 0 || mat_stride < 0)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "ld must be > 0 and mat_stride >= 0");
+    // 16-byte stores where a matrix's offset and ld are multiples of 4 doubles
+    if (((uintptr_t)e_dev & 15) != 0)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "e not 16-byte aligned");
     a.pts = pts_dev;
     a.cam_offs = cam_offs_dev;
     a.F = F_dev;

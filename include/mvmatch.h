@@ -182,6 +182,14 @@ void mvm_options_init(mvm_options *opts);
  *                                             (NaN counts as smallest; -1 if n_b == 0)
  *   minval_dev[...]                         = e[i][argmin] (NaN if n_b == 0)
  * dist_dev, argmin_dev and minval_dev may each be NULL (not produced).
+ * dist_offs_dev and row_offs_dev are the caller's: entry s*P + p is read on
+ * its own, so the matrices may lie in any order, with gaps between them and at
+ * any offset (a matrix whose offset or row length is not a multiple of 4 floats
+ * is stored element by element, the others 16 bytes per lane); nothing outside
+ * the matrices and row blocks is written.  dist_dev must be 16-byte aligned
+ * (MVM_ERR_INVALID_ARGUMENT before any launch otherwise: the store width is
+ * chosen from the offsets alone); argmin_dev and minval_dev need only their
+ * element's alignment.
  * pair_a / pair_b are HOST arrays of n_pairs camera indices (a != b).
  * max_n is a host-known upper bound on every view's detection count (n_a and
  * n_b over all (scene, pair)): it sizes the grid and the LDS column tile;
@@ -211,6 +219,8 @@ int mvm_pairwise_residual_argmin_ex(const double *pts_dev, const int64_t *cam_of
  * is a power of two in
  * [1, 256]; 1 is the unpitched layout of mvm_pairwise_residual_argmin_ex.
  * The caller sizes dist_dev and dist_offs_dev with the pitched sizes n_a*ld.
+ * Matrix offsets that are not multiples of row_align are taken as they are
+ * (rows then start off the lines; the results are the same).
  */
 int mvm_pairwise_residual_argmin_pitched(const double *pts_dev, const int64_t *cam_offs_dev,
                                          const double *F_dev, const int32_t *pair_a,
@@ -225,7 +235,11 @@ int mvm_pairwise_residual_argmin_pitched(const double *pts_dev, const int64_t *c
  * matrix (s, p) starts at e_dev + (s*P + p) * mat_stride and has row stride
  * ld (>= every n_b; use a multiple of 4 for vectorised stores).  This is the
  * exact fp64 value of epipolar_error (epipolar_matching.py:28) and the input
- * of the three-camera cube.
+ * of the three-camera cube.  Of a matrix's padding, columns n_b ..
+ * min(ld, roundup(n_b, 256)) - 1 of the rows i < n_a hold +inf; nothing else
+ * is written: not the rows from n_a on, the columns from roundup(n_b, 256) on,
+ * the rest of mat_stride, or anything past n_scenes * n_pairs * mat_stride.
+ * e_dev must be 16-byte aligned (MVM_ERR_INVALID_ARGUMENT otherwise).
  */
 int mvm_pairwise_residual_f64(const double *pts_dev, const int64_t *cam_offs_dev,
                               const double *F_dev, const int32_t *pair_a, const int32_t *pair_b,
@@ -244,6 +258,13 @@ int mvm_pairwise_residual_f64(const double *pts_dev, const int64_t *cam_offs_dev
  *                                            (N*M, P) cube row; -1 if P == 0)
  * max_n bounds every view's detection count.  workspace_dev must hold
  * mvm_triplet_workspace_bytes(n_scenes, max_n) bytes (16-byte aligned).
+ * cube_offs_dev and row_offs_dev are the caller's: entry s is read on its own
+ * (any order, gaps, any residue: a cube whose offset or P is not a multiple of
+ * 4 floats is stored in dword-aligned pieces); nothing outside the cubes and
+ * row blocks is written.  cube_dev must be 16-byte aligned
+ * (MVM_ERR_INVALID_ARGUMENT before any launch otherwise: the access width is
+ * chosen from the offsets alone); argmin_dev and minval_dev need only their
+ * element's alignment.
  */
 size_t mvm_triplet_workspace_bytes(int32_t n_scenes, int32_t max_n);
 int mvm_triplet_cost_argmin(const double *pts_dev, const int64_t *cam_offs_dev,
@@ -269,7 +290,9 @@ int mvm_triplet_cost_argmin_ex(const double *pts_dev, const int64_t *cam_offs_de
  * default shapes; with them requested, views of 33-48 take 32-j instead of
  * 48-j tiles) writes them itself; every other path reads them back from the
  * cube (cube_dev required).  Offsets that are multiples of 4 keys let the
- * kernel store 8 bytes per lane.
+ * kernel store 8 bytes per lane; any other offset is stored key by key.
+ * bmin8_offs_dev is the caller's (entry s read on its own), and bmin8_dev must
+ * be 8-byte aligned (MVM_ERR_INVALID_ARGUMENT before any launch otherwise).
  */
 int mvm_triplet_cost_argmin_bmin8(const double *pts_dev, const int64_t *cam_offs_dev,
                                   const double *F_dev, int32_t n_scenes, int32_t max_n,
@@ -286,7 +309,8 @@ int mvm_triplet_cost_argmin_bmin8(const double *pts_dev, const int64_t *cam_offs
  * those need:
  *   bmin8_dev  optional (NULL: not written): the same 16-bit 8-row minima
  *              mvm_triplet_cost_argmin_bmin8 writes (bit for bit, same layout
- *              and offsets);
+ *              and offsets; stored key by key, so any offset and a base
+ *              with a key's alignment);
  *   bm32_dev   the candidate-list kernels' 32-column block minima as 16-bit
  *              keys: for short-side column k of scene s, nb = ceil(M/32) *
  *              npad keys at bm32_dev + bm32_offs_dev[s] + k * nb (npad =
@@ -323,6 +347,8 @@ int mvm_triplet_minima(const double *pts_dev, const int64_t *cam_offs_dev, const
  * match_objects, bpc/inference/epipolar_matching.py:100-116, scipy 1.14's
  * shortest-augmenting-path algorithm, same tie-breaking and output order).
  * Problem p is the row-major float32 matrix at cost_dev + cost_offs_dev[p]
+ * (cost_offs_dev is the caller's, entry p read on its own; cost_dev needs only
+ * its element's alignment; ws_offs / out_offs are mvm_lsap_plan's)
  * with dims_dev[2p] rows and dims_dev[2p+1] columns (e.g. the flattened
  * (N*M, P) cube of mvm_triplet_cost_argmin).  Its min(rows, cols) assigned
  * (row, col) pairs go to row_ind_dev/col_ind_dev at out_offs_dev[p], sorted
@@ -422,7 +448,8 @@ void mvm_lsap_sparse_bounds(int32_t *min_cols, int32_t *max_cols, int32_t *max_s
  * candidate-list solver's counters for it (ABI 7): int32 [4] = dense scans for
  * a row's free minimum (no list, or no free entry left in it), dense scans for
  * the free ties at a search's end, rows whose candidate list overflowed,
- * Dijkstra steps.  Written by every solve of a problem of that class. */
+ * Dijkstra steps.  Written by every solve of a problem of that class; one that
+ * ends with a status other than 0 leaves all four 0. */
 int64_t mvm_lsap_sparse_stats_offset(int64_t rows, int64_t cols);
 int mvm_lsap_solve_resid(const int64_t *dims_dev, int32_t n_problems, const int64_t *ws_offs_dev,
                          const int64_t *out_offs_dev, void *workspace_dev, size_t workspace_bytes,

@@ -68,6 +68,21 @@ def assert_pairwise_equal(dev, pts, cam_offs, F, pairs, S, C, options=None):
 
 
 # ----------------------------------------------------------- pairwise ----
+# mvm_options of every pairwise kernel path (the argmin_path fixture's cases;
+# "_row_align" is the plan's row pitch, not an option)
+ARGMIN_PATHS = {"default": {}, "unpitched": {"_row_align": 1},
+                "interleaved": {"pairwise_row_interleave": 1},
+                "contiguous": {"pairwise_row_interleave": -1},
+                "interleaved_unpitched_rpw8": {"pairwise_row_interleave": 1, "_row_align": 1,
+                                               "pairwise_rows_per_wave": 8},
+                "eager": {"pairwise_argmin": "eager"},
+                "eager_unpitched": {"pairwise_argmin": "eager", "_row_align": 1},
+                "rpw8_rg2": {"pairwise_rows_per_wave": 8, "pairwise_row_groups": 2},
+                "rpw4": {"pairwise_rows_per_wave": 4},
+                "fronts3": {"pairwise_xcd_fronts": 3},
+                "fronts16_unpitched": {"pairwise_xcd_fronts": 16, "_row_align": 1}}
+
+
 @pytest.fixture(params=["default", "unpitched", "eager", "eager_unpitched", "rpw8_rg2", "rpw4",
                         "interleaved", "contiguous", "interleaved_unpitched_rpw8", "fronts3",
                         "fronts16_unpitched"])
@@ -81,17 +96,7 @@ def argmin_path(request):
     lines for ragged views) and some also unpitched (rows of n_b, the
     unaligned-row paths), and the XCD write-front counts forced (3, 16: ranges
     of unequal length per XCD)."""
-    return {"default": {}, "unpitched": {"_row_align": 1},
-            "interleaved": {"pairwise_row_interleave": 1},
-            "contiguous": {"pairwise_row_interleave": -1},
-            "interleaved_unpitched_rpw8": {"pairwise_row_interleave": 1, "_row_align": 1,
-                                           "pairwise_rows_per_wave": 8},
-            "eager": {"pairwise_argmin": "eager"},
-            "eager_unpitched": {"pairwise_argmin": "eager", "_row_align": 1},
-            "rpw8_rg2": {"pairwise_rows_per_wave": 8, "pairwise_row_groups": 2},
-            "rpw4": {"pairwise_rows_per_wave": 4},
-            "fronts3": {"pairwise_xcd_fronts": 3},
-            "fronts16_unpitched": {"pairwise_xcd_fronts": 16, "_row_align": 1}}[request.param]
+    return ARGMIN_PATHS[request.param]
 
 
 @pytest.mark.parametrize("S,C,n,ragged", [(3, 4, 256, False), (5, 4, 300, True), (2, 4, 1024, False),
@@ -291,6 +296,30 @@ KPL_MAX_VIEW = {"fused_kpl3": 192, "fused_kpl5": 160, "fused_kpl6": 192, "fused_
                 "fused_rows2_kpl8": 256, "fused_tile32_kpl5": 160}
 
 
+# mvm_options of every cube kernel path (the cube_path fixture's cases)
+CUBE_PATHS = {"default": {}, "small": {"cube_kernel": "small"},
+              "fused": {"cube_kernel": "fused"},
+              "fused_rows2": {"cube_kernel": "fused", "cube_rows_per_instr": 2},
+              "fused_rows1": {"cube_kernel": "fused", "cube_rows_per_instr": 1},
+              "fused_kpl4": {"cube_kernel": "fused", "cube_cols_per_lane": 4},
+              "fused_rows1_kpl4": {"cube_kernel": "fused", "cube_rows_per_instr": 1,
+                  "cube_cols_per_lane": 4},
+              "fused_kpl3": {"cube_kernel": "fused", "cube_cols_per_lane": 3},
+              "fused_kpl5": {"cube_kernel": "fused", "cube_cols_per_lane": 5},
+              "fused_kpl6": {"cube_kernel": "fused", "cube_cols_per_lane": 6},
+              "fused_kpl7": {"cube_kernel": "fused", "cube_cols_per_lane": 7},
+              "fused_rows2_kpl8": {"cube_kernel": "fused", "cube_rows_per_instr": 2,
+                  "cube_cols_per_lane": 8},
+              "fused_tile32": {"cube_kernel": "fused", "cube_tile_rows": 32},
+              "fused_rows8_tile16": {"cube_kernel": "fused", "cube_rows_per_instr": 8,
+                  "cube_tile_rows": 16},
+              "fused_rows4": {"cube_kernel": "fused", "cube_rows_per_instr": 4},
+              "fused_tile32_kpl5": {"cube_kernel": "fused", "cube_tile_rows": 32,
+                  "cube_cols_per_lane": 5},
+              "workspace": {"cube_kernel": "workspace"},
+              "generic": {"cube_kernel": "generic"}}
+
+
 @pytest.fixture(params=["default", "small", "fused", "fused_rows2", "fused_rows1", "fused_kpl4",
                         "fused_rows1_kpl4", "fused_kpl3", "fused_kpl5", "fused_kpl6", "fused_kpl7",
                         "fused_rows2_kpl8", "fused_tile32",
@@ -308,27 +337,7 @@ def cube_path(request):
     32 i rows (tile32: the split forms; one row per instruction keeps 16) -- the
     tiled kernel over the fp64 workspace (beyond 256: the generic kernel) and
     the generic kernel."""
-    return request.param, {"default": {}, "small": {"cube_kernel": "small"},
-                           "fused": {"cube_kernel": "fused"},
-                           "fused_rows2": {"cube_kernel": "fused", "cube_rows_per_instr": 2},
-                           "fused_rows1": {"cube_kernel": "fused", "cube_rows_per_instr": 1},
-                           "fused_kpl4": {"cube_kernel": "fused", "cube_cols_per_lane": 4},
-                           "fused_rows1_kpl4": {"cube_kernel": "fused", "cube_rows_per_instr": 1,
-                                                "cube_cols_per_lane": 4},
-                           "fused_kpl3": {"cube_kernel": "fused", "cube_cols_per_lane": 3},
-                           "fused_kpl5": {"cube_kernel": "fused", "cube_cols_per_lane": 5},
-                           "fused_kpl6": {"cube_kernel": "fused", "cube_cols_per_lane": 6},
-                           "fused_kpl7": {"cube_kernel": "fused", "cube_cols_per_lane": 7},
-                           "fused_rows2_kpl8": {"cube_kernel": "fused", "cube_rows_per_instr": 2,
-                                                "cube_cols_per_lane": 8},
-                           "fused_tile32": {"cube_kernel": "fused", "cube_tile_rows": 32},
-                           "fused_rows8_tile16": {"cube_kernel": "fused", "cube_rows_per_instr": 8,
-                                                  "cube_tile_rows": 16},
-                           "fused_rows4": {"cube_kernel": "fused", "cube_rows_per_instr": 4},
-                           "fused_tile32_kpl5": {"cube_kernel": "fused", "cube_tile_rows": 32,
-                                                 "cube_cols_per_lane": 5},
-                           "workspace": {"cube_kernel": "workspace"},
-                           "generic": {"cube_kernel": "generic"}}[request.param]
+    return request.param, CUBE_PATHS[request.param]
 
 
 def test_cube_golden_batched(cuda, golden, cube_path):

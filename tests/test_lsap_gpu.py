@@ -24,6 +24,25 @@ def _batched(cuda, mats, options=None, dtype=np.float32):
     return [(r[o[k]:o[k + 1]], c[o[k]:o[k + 1]], int(st[k])) for k in range(len(mats))]
 
 
+# mvm_options of every assignment kernel class (the lsap_path fixture's cases)
+_OFF = {"lsap_wave_max_cols": -1, "lsap_multi_g": -1, "lsap_mreg_max_cols": -1,
+        "lsap_sparse_min_cols": -1}
+_NOREG = dict(_OFF, lsap_reg_max_cols=-1)
+LSAP_PATHS = {"default": None, "reg": _OFF, "reg1024": dict(_OFF, lsap_reg_threads=1024),
+              "mreg": {"lsap_wave_max_cols": -1, "lsap_reg_max_cols": -1, "lsap_multi_g": -1,
+                       "lsap_sparse_min_cols": -1},
+              "lds": _NOREG,
+              "workgroup": dict(_NOREG, lsap_lds_max_cols=-1),
+              "workgroup256": dict(_NOREG, lsap_lds_max_cols=-1, lsap_mid_max_cols=1000000),
+              "multi": {"lsap_wave_max_cols": -1, "lsap_multi_g": 4, "lsap_mreg_max_cols": -1,
+                       "lsap_sparse_min_cols": -1},
+              "nomreg": {"lsap_mreg_max_cols": -1, "lsap_sparse_min_cols": -1},
+              "sparse": {"lsap_wave_max_cols": -1, "lsap_sparse_min_cols": 1},
+              "sparse_lo": {"lsap_sparse_min_cols": 1025},
+              "sparse_tb1": {"lsap_wave_max_cols": -1, "lsap_sparse_min_cols": 1, "lsap_sparse_blocks": 1},
+              "sparse_tb64": {"lsap_sparse_min_cols": 1025, "lsap_sparse_blocks": 64}}
+
+
 @pytest.fixture(params=["default", "reg", "reg1024", "mreg", "lds", "workgroup", "workgroup256", "multi",
                         "nomreg", "sparse", "sparse_lo", "sparse_tb1", "sparse_tb64"])
 def lsap_path(request):
@@ -47,22 +66,7 @@ def lsap_path(request):
     sparse_tb64: one / 64 candidate blocks per row (short lists that run out,
     so rows fall back to dense scans, and long ones).  Every other path
     turns the candidate-list class off."""
-    off = {"lsap_wave_max_cols": -1, "lsap_multi_g": -1, "lsap_mreg_max_cols": -1,
-           "lsap_sparse_min_cols": -1}
-    noreg = dict(off, lsap_reg_max_cols=-1)
-    return {"default": None, "reg": off, "reg1024": dict(off, lsap_reg_threads=1024),
-            "mreg": {"lsap_wave_max_cols": -1, "lsap_reg_max_cols": -1, "lsap_multi_g": -1,
-                     "lsap_sparse_min_cols": -1},
-            "lds": noreg,
-            "workgroup": dict(noreg, lsap_lds_max_cols=-1),
-            "workgroup256": dict(noreg, lsap_lds_max_cols=-1, lsap_mid_max_cols=1000000),
-            "multi": {"lsap_wave_max_cols": -1, "lsap_multi_g": 4, "lsap_mreg_max_cols": -1,
-                      "lsap_sparse_min_cols": -1},
-            "nomreg": {"lsap_mreg_max_cols": -1, "lsap_sparse_min_cols": -1},
-            "sparse": {"lsap_wave_max_cols": -1, "lsap_sparse_min_cols": 1},
-            "sparse_lo": {"lsap_sparse_min_cols": 1025},
-            "sparse_tb1": {"lsap_wave_max_cols": -1, "lsap_sparse_min_cols": 1, "lsap_sparse_blocks": 1},
-            "sparse_tb64": {"lsap_sparse_min_cols": 1025, "lsap_sparse_blocks": 64}}[request.param]
+    return LSAP_PATHS[request.param]
 
 
 def test_random_shapes_and_ties_batched(cuda, lsap_path):
