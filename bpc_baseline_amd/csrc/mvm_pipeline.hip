@@ -265,7 +265,14 @@ struct SelSrc {
     const float *cb;
     const double *e12, *e13t, *e23t;   // e12 != nullptr: the residual form
     int64_t M, P;
+    int64_t rows;   // N * M
     int ld;
+    // the value select compares: the entry's, or +inf (kept under no threshold)
+    // for a pair that is not an index of the scene's (N*M, P) problem -- what a
+    // problem whose assignment failed leaves in its row_ind / col_ind region
+    __device__ __forceinline__ float at_checked(int64_t r, int64_t k) const {
+        return (r >= 0 && r < rows && k >= 0 && k < P) ? at(r, k) : INFINITY;
+    }
     __device__ __forceinline__ float at(int64_t r, int64_t k) const {
         if (e12) {
             const int64_t i = r / M, j = r - i * M;
@@ -289,6 +296,7 @@ __global__ __launch_bounds__(kSelThreads) void select_triangulate_kernel(
     SelSrc cb{};
     cb.M = M;
     cb.P = P;
+    cb.rows = (c1 - c0) * M;
     if (resid) {
         cb.ld = rld;
         cb.e12 = resid + (int64_t)s * rstride;
@@ -302,14 +310,14 @@ __global__ __launch_bounds__(kSelThreads) void select_triangulate_kernel(
         const int64_t m = m0 + t;
         float mine = INFINITY;
         if (m < n) {
-            const float v = cb.at(row_ind[o + m], col_ind[o + m]);
+            const float v = cb.at_checked(row_ind[o + m], col_ind[o + m]);
             if ((double)v < threshold) mine = v;
         }
         int64_t rank = 0;
         for (int64_t q0 = 0; q0 < n; q0 += kSelTile) {
             __syncthreads();
             for (int q = t; q < kSelTile && q0 + q < n; q += kSelThreads) {
-                const float v = cb.at(row_ind[o + q0 + q], col_ind[o + q0 + q]);
+                const float v = cb.at_checked(row_ind[o + q0 + q], col_ind[o + q0 + q]);
                 s_cost[q] = (double)v < threshold ? v : INFINITY;
             }
             __syncthreads();

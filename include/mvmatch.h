@@ -435,8 +435,25 @@ int mvm_lsap_solve_ex3(const void *cost_dev, int32_t cost_dtype, const int64_t *
  * candidate lists only: ~0.3 MB per 256^3 scene).
  * Statuses of every mvm_lsap_solve* entry point: 0 ok, 1 NaN / -inf entries
  * (scipy's ValueError), 2 infeasible, 3 internal (a co-resident wait timed
- * out), 4 the problem exceeds the bounds the call was given (short_max /
- * long_max) or, here, is outside the class.
+ * out), 4 refused by the candidate-list class (below).
+ * The host bounds (long_min / long_max / short_max) are a contract, not a
+ * check: long_min <= every non-empty problem's long side <= long_max and every
+ * short side <= short_max.  They may be as loose as the caller likes (a
+ * capacity instead of the batch's maxima; mvm_lsap_solve passes (1,
+ * INT64_MAX)): the classes are then all launched, each problem is still
+ * solved by exactly one of them, and the results are the same.  What happens
+ * to a problem past them depends on the class that owns it:
+ *   - the candidate-list class (mvm_lsap_sparse.hip) sizes its LDS from
+ *     min(short_max, 1024) and min(long_max, 65536) and REFUSES a problem of
+ *     its class past either with status 4 (no assignment, its counters 0); in
+ *     mvm_lsap_solve_resid it also gives status 4 to a problem outside the
+ *     class, which no other kernel could solve without a cube;
+ *   - the dense classes (mvm_lsap.hip: one wave, register state, split
+ *     register state, split workspace state, LDS state, workspace state)
+ *     contain no such refusal: they size dynamic LDS from the bounds and skip
+ *     launches by them, so for their problems the bounds MUST HOLD -- a problem
+ *     past them may be left unsolved (its status not written) or run a kernel
+ *     with too little LDS.
  */
 int64_t mvm_lsap_plan_resid(int32_t n_problems, const int64_t *rows, const int64_t *cols,
                             int64_t *ws_offs, int64_t *out_offs);
@@ -509,7 +526,16 @@ int mvm_triangulate_dlt(const double *proj_dev, const int32_t *set_of_point_dev,
  * centroids pts_dev (CSR cam_offs_dev, 3 views per scene) with the scene's
  * projection matrices proj_dev [S, 3, 3, 4] (K @ RT[:3], :86-94).  Match w
  * of scene s (w < count_dev[s]) is written at lsap_out_offs_dev[s] + w:
- * match_dev int32 [.., 3] = (i, j, k), cost_dev f32, X_dev f64 [.., 3].
+ * match_dev int32 [.., 3] = (i, j, k), cost_dev f32, X_dev f64 [.., 3]; rows
+ * from count_dev[s] on are not written.
+ * A pair (r, c) that is not an index of the scene's problem (r outside
+ * [0, N*M) or c outside [0, P)) is ignored, as one over the threshold is: no
+ * index is used unchecked.  A problem whose status is not 0 got no
+ * assignment, and its row_ind / col_ind region holds what it held before
+ * (uninitialised memory, an earlier batch's indices): the launch stays inside
+ * its buffers whatever that is, and the pairs among it that are indices are
+ * selected like any other, so a caller looks at status_dev before it uses
+ * that scene's matches.
  */
 int mvm_select_triangulate(const float *cube_dev, const int64_t *cube_offs_dev,
                            const int64_t *cam_offs_dev, const int64_t *lsap_out_offs_dev,

@@ -54,7 +54,8 @@ def select_sort(cube_flat: np.ndarray, M: int, P: int, row_ind: np.ndarray, col_
     Assignment m of the flattened (N*M, P) float32 cube is kept iff
     ``float(np.float32(v_m)) < float(threshold)``: an explicit float64 compare,
     the contract of include/mvmatch.h, whatever the installed NumPy would
-    promote a float32 scalar against a Python number to.  Kept entries are
+    promote a float32 scalar against a Python number to.  A pair (r, c) with r
+    outside [0, N*M) or c outside [0, P) is dropped first.  Kept entries are
     decoded ``i = r // M, j = r % M, k = c`` and ordered by a stable sort of
     their float32 costs (Python's sorted: ties keep the assignment's order).
     -> (match int32 [k, 3], cost float32 [k]).
@@ -62,6 +63,10 @@ def select_sort(cube_flat: np.ndarray, M: int, P: int, row_ind: np.ndarray, col_
     cube_flat = np.asarray(cube_flat, np.float32).reshape(-1)
     r = np.asarray(row_ind, np.int64).reshape(-1)
     c = np.asarray(col_ind, np.int64).reshape(-1)
+    # a pair that is no index of the (N*M, P) problem is ignored (a failed
+    # assignment's region holds whatever it held before)
+    ok = (r >= 0) & (r < cube_flat.size // P) & (c >= 0) & (c < P) if P > 0 else np.zeros(r.size, bool)
+    r, c = r[ok], c[ok]
     if r.size == 0:
         return np.zeros((0, 3), np.int32), np.zeros(0, np.float32)
     v = cube_flat[r * P + c]
