@@ -240,10 +240,116 @@ __global__ __launch_bounds__(256) void dlt_kernel(const double *proj, const int3
     X[3 * p + 2] = out[2];
 }
 
-template <int NV>
-void launch_dlt(const double *proj, const int32_t *sop, const double *pts2d, int32_t n, double *X,
-                hipStream_t s) {
-    dlt_kernel<NV><<<(n + 255) / 256, 256, 0, s>>>(proj, sop, pts2d, n, X);
+// ------------------------------- shared by the match and view kernels ----
+// The pieces the kernels below have in common, each written once.
+constexpr int kCompactThreads = 256;
+constexpr int kCompactScenes = kCompactThreads / 64;
+
+// One wave per item (a capture, or one view of a capture), four items to a
+// workgroup, lanes striding over the item's rows: no LDS, no barrier.  The
+// wave's item comes back as a scalar, so what it indexes (offsets, the
+// capture's P) is read by scalar loads ahead of the row loop; -1 beyond n_items.
+__device__ __forceinline__ int64_t wave_item(int64_t n_items, int &lane) {
+    lane = threadIdx.x % 64;
+    const int64_t item = (int64_t)blockIdx.x * kCompactScenes +
+                         __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    return item < n_items ? item : -1;
+}
+
+// capture s's matches: rows mo .. mo + n, never more than match_offs leaves it
+struct MatchRange { int64_t mo, n; };
+__device__ __forceinline__ MatchRange match_range(const int64_t *match_offs, const int32_t *count,
+                                                  int64_t s) {
+    const int64_t mo = match_offs[s];
+    return {mo, min<int64_t>(count[s], match_offs[s + 1] - mo)};
+}
+
+// The view rule.  vw: a row's C view slots, co: its capture's cam_offs (C + 1
+// entries are readable: cam_offs holds C S + 1).  A slot c < n_cams with
+// v >= 0 is kept (its bit in the mask) if v is a detection of its view,
+// v < co[c + 1] - co[c]; if it is not, the row is not `ok` and no index of it
+// may be used.  A slot < 0 is no view and says nothing about `ok`.  The slot
+// loop is compile-time under `c < n_cams`.
+//  * refine_points_kernel asked exactly this of every slot; a seed < 0 is not
+//    in the mask, and fewer than two kept views are its status 3, not `!ok`.
+//  * prune_views_kernel asked `0 <= v < size` of the seeds and `v < size` of
+//    the extras (negative: no view), kept the extras >= 0, and left a row that
+//    failed alone: seeded_views, below -- a seed passes the old test exactly
+//    when its bit is set, and `ok` covers an extra that is >= 0 and too large.
+//  * extend_select_triangulate_kernel asked the same of the seeds and kept the
+//    extras by sign alone.  It wrote those slots itself: -1, or an l it had
+//    checked against nd = co[3 + e + 1] - co[3 + e], the size the rule reads,
+//    so the size test it now makes of them never fails: seeded_views again.
+__device__ __forceinline__ uint32_t kept_views(const int32_t *vw, const int64_t *co, int n_cams,
+                                               bool &ok) {
+    uint32_t mask = 0u;
+    ok = true;
+#pragma unroll
+    for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+        if (c < n_cams) {
+            const int32_t v = vw[c];
+            const bool in_view = v < co[c + 1] - co[c];
+            if (v >= 0 && in_view) mask |= 1u << c;
+            ok &= v < 0 || in_view;
+        }
+    }
+    return mask;
+}
+
+// kept_views of a row that stands on its three seeds: the mask, or 7 (no
+// extra view: the row is left as it is) when the row is not ok or a seed is not kept
+__device__ __forceinline__ uint32_t seeded_views(const int32_t *vw, const int64_t *co, int n_cams) {
+    bool ok;
+    const uint32_t mask = kept_views(vw, co, n_cams, ok);
+    return ok && (mask & 7u) == 7u ? mask : 7u;
+}
+
+// the centroids of the views of `mask` (kept views: every index is checked),
+// by compile-time slot: no register array is indexed by a runtime value
+__device__ __forceinline__ void gather_centroids(const double *pts, const int64_t *co,
+                                                 const int32_t *vw, uint32_t mask,
+                                                 double (&cx)[MVM_MAX_CAMS],
+                                                 double (&cy)[MVM_MAX_CAMS]) {
+#pragma unroll
+    for (int c = 0; c < MVM_MAX_CAMS; ++c) {
+        if ((mask >> c) & 1u) {
+            const int64_t row = co[c] + vw[c];
+            cx[c] = pts[2 * row];
+            cy[c] = pts[2 * row + 1];
+        }
+    }
+}
+
+// h = P (X, 1) for a row-major 3x4 P: every product and sum rounded on its
+// own (this file's fp contract(off)), associated ((p0 X0 + p1 X1) + p2 X2) + p3
+struct Homog { double h0, h1, h2; };
+__device__ __forceinline__ Homog project(const double *p, double X0, double X1, double X2) {
+    return {((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3], ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7],
+            ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11]};
+}
+
+// One detection row -- a 16-byte box and a 16-byte centroid -- read from row
+// `row` of the packer's arrays, or written to row o of a table's.  VEC: as
+// 16-byte accesses (every base 16-byte aligned), else element by element.
+struct Detection { int4 box; double2 cent; };
+template <bool VEC>
+__device__ __forceinline__ Detection load_detection(const int32_t *boxes, const double *pts, int64_t row) {
+    if (VEC)
+        return {reinterpret_cast<const int4 *>(boxes)[row], reinterpret_cast<const double2 *>(pts)[row]};
+    return {make_int4(boxes[4 * row], boxes[4 * row + 1], boxes[4 * row + 2], boxes[4 * row + 3]),
+            make_double2(pts[2 * row], pts[2 * row + 1])};
+}
+template <bool VEC>
+__device__ __forceinline__ void store_detection(int32_t *boxes_out, double *cent_out, int64_t o,
+                                                const Detection &d) {
+    if (VEC) {
+        reinterpret_cast<int4 *>(boxes_out)[o] = d.box;
+        reinterpret_cast<double2 *>(cent_out)[o] = d.cent;
+    } else {
+        boxes_out[4 * o] = d.box.x, boxes_out[4 * o + 1] = d.box.y;
+        boxes_out[4 * o + 2] = d.box.z, boxes_out[4 * o + 3] = d.box.w;
+        cent_out[2 * o] = d.cent.x, cent_out[2 * o + 1] = d.cent.y;
+    }
 }
 
 // ------------------------------------------- select + triangulate ----
@@ -383,6 +489,19 @@ __device__ __forceinline__ void extend_dlt(const double *proj_s, const double *p
     dlt_point<NV>(P, xy, X);
 }
 
+// extend_dlt<V> over the V = popcount(mask) views of the mask, instantiated
+// for LO .. HI only (a count above HI takes HI's, as a switch's default would)
+template <int LO, int HI>
+__device__ __forceinline__ void mask_dlt(const double *proj_s, const double *pts, const int64_t *co,
+                                         const int32_t *vw, uint32_t mask, double X[3]) {
+    if constexpr (LO < HI) {
+        if (__builtin_popcount(mask) == LO) return extend_dlt<LO>(proj_s, pts, co, vw, mask, X);
+        return mask_dlt<LO + 1, HI>(proj_s, pts, co, vw, mask, X);
+    } else {
+        extend_dlt<HI>(proj_s, pts, co, vw, mask, X);
+    }
+}
+
 __global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
     const float *E, const int64_t *ext_offs, const int64_t *lsap_offs, const int64_t *row_ind,
     const int64_t *col_ind, const int32_t *match, const int64_t *match_offs, const int32_t *count,
@@ -391,8 +510,7 @@ __global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
     const int64_t s = blockIdx.x;
     const int t = threadIdx.x;
     const int n_ext = n_cams - 3;
-    const int64_t mo = match_offs[s];
-    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
+    const auto [mo, n] = match_range(match_offs, count, s);
     const int64_t *co = cam_offs + s * n_cams;
     for (int64_t w = t; w < n; w += kSelThreads) {
         int32_t *vw = views + (mo + w) * n_cams;
@@ -424,20 +542,10 @@ __global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
     const double *proj_s = proj + s * n_cams * 12;
     for (int64_t w = t; w < n; w += kSelThreads) {
         const int32_t *vw = views + (mo + w) * n_cams;
-        uint32_t mask = 7u;
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ok &= vw[c] >= 0 && vw[c] < co[c + 1] - co[c];
-        for (int c = 3; c < n_cams; ++c) mask |= (vw[c] >= 0 ? 1u : 0u) << c;
-        if (!ok || mask == 7u) continue;      // the three-view X stands
+        const uint32_t mask = seeded_views(vw, co, n_cams);
+        if (mask == 7u) continue;             // the three-view X stands
         double out[3];
-        switch (__builtin_popcount(mask)) {
-            case 4: extend_dlt<4>(proj_s, pts, co, vw, mask, out); break;
-            case 5: extend_dlt<5>(proj_s, pts, co, vw, mask, out); break;
-            case 6: extend_dlt<6>(proj_s, pts, co, vw, mask, out); break;
-            case 7: extend_dlt<7>(proj_s, pts, co, vw, mask, out); break;
-            default: extend_dlt<8>(proj_s, pts, co, vw, mask, out); break;
-        }
+        mask_dlt<4, 8>(proj_s, pts, co, vw, mask, out);
         X[3 * (mo + w) + 0] = out[0];
         X[3 * (mo + w) + 1] = out[1];
         X[3 * (mo + w) + 2] = out[2];
@@ -448,22 +556,16 @@ __global__ __launch_bounds__(kSelThreads) void extend_select_triangulate_kernel(
 // The select kernels leave scene s's matches at lsap_offs[s] with slack rows
 // behind them, as per-view indices.  This copies them to dense rows
 // dense_offs[s] + w and resolves the indices against the packer's rows, so a
-// row stands on its own (mvm_compact_matches).  One wave per scene, lanes
-// stride over its matches: no LDS, no barrier.  VEC: boxes / pts rows and
-// their triples move as 16-byte accesses (every base 16-byte aligned).
-constexpr int kCompactThreads = 256;
-constexpr int kCompactScenes = kCompactThreads / 64;
+// row stands on its own (mvm_compact_matches).  One wave per scene
+// (wave_item); VEC: the detection rows move as 16-byte accesses.
 
 // The reprojection residual of X in one view (include/mvmatch.h,
 // mvm_compact_matches_views): p the view's row-major 3x4 P, (cx, cy) its
-// centroid.  Every product and sum is rounded on its own (this file's fp
-// contract(off)), the divisions and the square root are IEEE.
+// centroid.  `project`, then IEEE divisions and square root.
 __device__ __forceinline__ double reproj_residual(const double *p, double X0, double X1, double X2,
                                                   double cx, double cy) {
-    const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
-    const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
-    const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
-    const double du = h0 / h2 - cx, dv = h1 / h2 - cy;
+    const Homog h = project(p, X0, X1, X2);
+    const double du = h.h0 / h.h2 - cx, dv = h.h1 / h.h2 - cy;
     return sqrt(du * du + dv * dv);
 }
 
@@ -476,9 +578,9 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
     int32_t scene_base, int32_t *__restrict__ scene_out, int32_t *__restrict__ match_out,
     float *__restrict__ cost_out, double *__restrict__ X_out, int32_t *__restrict__ boxes_out,
     double *__restrict__ cent_out) {
-    const int lane = threadIdx.x % 64;
-    const int64_t s = (int64_t)blockIdx.x * kCompactScenes + threadIdx.x / 64;
-    if (s >= n_scenes) return;
+    int lane;
+    const int64_t s = wave_item(n_scenes, lane);
+    if (s < 0) return;
     const int64_t src = seg_offs[s], dst = dense_offs[s];
     const int32_t n = count[s];
     const int64_t c[3] = {cam_offs[3 * s], cam_offs[3 * s + 1], cam_offs[3 * s + 2]};
@@ -495,29 +597,19 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_kernel(
             X_out[3 * r + v] = X[3 * a + v];
         }
 #pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            const int64_t row = c[v] + m[v], o = 3 * r + v;
-            if (VEC) {
-                reinterpret_cast<int4 *>(boxes_out)[o] = reinterpret_cast<const int4 *>(boxes)[row];
-                reinterpret_cast<double2 *>(cent_out)[o] = reinterpret_cast<const double2 *>(pts)[row];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = boxes[4 * row + q];
-                cent_out[2 * o] = pts[2 * row];
-                cent_out[2 * o + 1] = pts[2 * row + 1];
-            }
-        }
+        for (int v = 0; v < 3; ++v)
+            store_detection<VEC>(boxes_out, cent_out, 3 * r + v, load_detection<VEC>(boxes, pts, c[v] + m[v]));
     }
 }
 
 // The table of a C-camera batch (mvm_compact_matches_views): the same copy
 // over the C view slots of mvm_extend_select_triangulate's rows, -1 slots
 // filled with (-1, -1, -1, -1) / NaN, plus the reprojection residual of X in
-// every kept view.  The capture's P (12 C doubles) and cam_offs are the same
-// for every lane of the wave: loaded once, ahead of the match loop and of
-// every store.  The camera slot is a compile-time index (MVM_MAX_CAMS slots,
-// `c < n_cams` predicated), so P and co stay in registers.  Every product and
-// sum of the residual is rounded on its own (this file's fp contract(off)).
+// every kept view (reproj_residual).  The capture's P (12 C doubles) and
+// cam_offs are the same for every lane of the wave (wave_item): loaded once,
+// ahead of the match loop and of every store.  The camera slot is a
+// compile-time index (MVM_MAX_CAMS slots, `c < n_cams` predicated), so P and
+// co stay in registers.
 template <bool VEC>
 __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
     const int32_t *__restrict__ views, const float *__restrict__ cost,
@@ -529,11 +621,9 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
     int32_t *__restrict__ scene_out, int32_t *__restrict__ views_out, int32_t *__restrict__ nviews_out,
     float *__restrict__ cost_out, float *__restrict__ ext_cost_out, double *__restrict__ X_out,
     int32_t *__restrict__ boxes_out, double *__restrict__ cent_out, double *__restrict__ reproj_out) {
-    const int lane = threadIdx.x % 64;
-    // the wave's capture as a scalar, so its P and offsets are scalar loads
-    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
-                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-    if (s >= n_scenes) return;
+    int lane;
+    const int64_t s = wave_item(n_scenes, lane);
+    if (s < 0) return;
     const int64_t src = seg_offs[s], dst = dense_offs[s];
     const int32_t n = count[s];
     const int n_ext = n_cams - 3;
@@ -566,33 +656,12 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
                 views_out[o] = v;
                 if (v >= 0) {
                     ++kept;
-                    const int64_t row = co[c] + v;
-                    double cx, cy;
-                    if (VEC) {
-                        reinterpret_cast<int4 *>(boxes_out)[o] = reinterpret_cast<const int4 *>(boxes)[row];
-                        const double2 p = reinterpret_cast<const double2 *>(pts)[row];
-                        reinterpret_cast<double2 *>(cent_out)[o] = p;
-                        cx = p.x;
-                        cy = p.y;
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = boxes[4 * row + q];
-                        cx = pts[2 * row];
-                        cy = pts[2 * row + 1];
-                        cent_out[2 * o] = cx;
-                        cent_out[2 * o + 1] = cy;
-                    }
-                    reproj_out[o] = reproj_residual(P + 12 * c, X0, X1, X2, cx, cy);
+                    const Detection d = load_detection<VEC>(boxes, pts, co[c] + v);
+                    store_detection<VEC>(boxes_out, cent_out, o, d);
+                    reproj_out[o] = reproj_residual(P + 12 * c, X0, X1, X2, d.cent.x, d.cent.y);
                 } else {
-                    if (VEC) {
-                        reinterpret_cast<int4 *>(boxes_out)[o] = make_int4(-1, -1, -1, -1);
-                        reinterpret_cast<double2 *>(cent_out)[o] = make_double2(qnan, qnan);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) boxes_out[4 * o + q] = -1;
-                        cent_out[2 * o] = qnan;
-                        cent_out[2 * o + 1] = qnan;
-                    }
+                    store_detection<VEC>(boxes_out, cent_out, o,
+                                         {make_int4(-1, -1, -1, -1), make_double2(qnan, qnan)});
                     reproj_out[o] = qnan;
                 }
             }
@@ -605,14 +674,13 @@ __global__ __launch_bounds__(kCompactThreads) void compact_matches_views_kernel(
 // mvm_prune_views_triangulate: per match of a C-camera batch,
 // drop the extra views whose reprojection residual exceeds `gate`, the worst
 // one at a time, and triangulate again over what is left after every drop.
-// The shape of compact_matches_views_kernel: one wave per capture (its index
-// a scalar, so the extra cameras' P and the capture's cam_offs are scalar
-// loads ahead of the match loop), four captures per workgroup, lanes striding
-// over the capture's matches; no LDS, no barrier.  The kept set is a bit
-// mask; the worst view is chosen over compile-time camera slots under the
-// mask's bit, and the DLT gathers by constant slot (extend_dlt), so no
-// register array is indexed by a runtime value.  A row that drops nothing is
-// not written (its `pruned` word is 0).
+// One wave per capture (wave_item), so the extra cameras' P and the capture's
+// cam_offs are scalar loads ahead of the match loop.  The kept set is the bit
+// mask of seeded_views (a row that fails the view rule is left alone); the
+// worst view is chosen over compile-time camera slots under the mask's bit,
+// and the DLT gathers by constant slot (mask_dlt), so no register array is
+// indexed by a runtime value.  A row that drops nothing is not written (its
+// `pruned` word is 0).
 constexpr int kPruneSlots = MVM_MAX_CAMS - 3;    // the extra cameras 3 .. 7
 
 __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
@@ -620,55 +688,25 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
     const double *__restrict__ pts, const int64_t *__restrict__ cam_offs,
     const double *__restrict__ proj, double gate, int32_t n_scenes, int32_t n_cams, int32_t *views,
     float *ext_cost, double *X, int32_t *__restrict__ pruned) {
-    const int lane = threadIdx.x % 64;
-    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
-                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-    if (s >= n_scenes) return;
-    const int64_t mo = match_offs[s];
-    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
+    int lane;
+    const int64_t s = wave_item(n_scenes, lane);
+    if (s < 0) return;
+    const auto [mo, n] = match_range(match_offs, count, s);
     const int n_ext = n_cams - 3;
     const int64_t *co_s = cam_offs + s * n_cams;
     const double *proj_s = proj + s * n_cams * 12;
-    // n_cams >= 4: co_s[3] closes the third seed view
-    const int64_t seed_n[3] = {co_s[1] - co_s[0], co_s[2] - co_s[1], co_s[3] - co_s[2]};
-    int64_t co[kPruneSlots], view_n[kPruneSlots];
     double P[12 * kPruneSlots];
 #pragma unroll
-    for (int e = 0; e < kPruneSlots; ++e) {
-        if (e < n_ext) {
-            co[e] = co_s[3 + e];
-            view_n[e] = co_s[3 + e + 1] - co[e];     // cam_offs holds C S + 1 entries
+    for (int e = 0; e < kPruneSlots; ++e)
+        if (e < n_ext)
 #pragma unroll
             for (int k = 0; k < 12; ++k) P[12 * e + k] = proj_s[12 * (3 + e) + k];
-        }
-    }
     for (int64_t w = lane; w < n; w += 64) {
         const int64_t row = mo + w;
         int32_t *vw = views + row * n_cams;
-        // extend_select_triangulate_kernel's `ok`: a seed outside its view leaves the row
-        // alone; so does an extra-view entry that is neither negative (no
-        // detection) nor a detection of its view -- no index is used unchecked
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ok &= vw[c] >= 0 && vw[c] < seed_n[c];
-        int32_t ve[kPruneSlots];
-#pragma unroll
-        for (int e = 0; e < kPruneSlots; ++e) {
-            if (e < n_ext) {
-                ve[e] = vw[3 + e];
-                ok &= ve[e] < view_n[e];
-            }
-        }
-        uint32_t mask = 7u, dropped = 0u;
-        double cx[kPruneSlots], cy[kPruneSlots];
-#pragma unroll
-        for (int e = 0; e < kPruneSlots; ++e) {
-            if (e < n_ext && ok && ve[e] >= 0) {
-                mask |= 1u << (3 + e);
-                cx[e] = pts[2 * (co[e] + ve[e])];
-                cy[e] = pts[2 * (co[e] + ve[e]) + 1];
-            }
-        }
+        uint32_t mask = seeded_views(vw, co_s, n_cams), dropped = 0u;
+        double cx[MVM_MAX_CAMS], cy[MVM_MAX_CAMS];
+        gather_centroids(pts, co_s, vw, mask & ~7u, cx, cy);     // the seeds are never candidates
         if (mask != 7u) {
             double X0 = X[3 * row], X1 = X[3 * row + 1], X2 = X[3 * row + 2];
             for (int pass = 0; pass < n_ext; ++pass) {
@@ -680,7 +718,7 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
 #pragma unroll
                 for (int e = 0; e < kPruneSlots; ++e) {
                     if ((mask >> (3 + e)) & 1u) {
-                        const double r = reproj_residual(P + 12 * e, X0, X1, X2, cx[e], cy[e]);
+                        const double r = reproj_residual(P + 12 * e, X0, X1, X2, cx[3 + e], cy[3 + e]);
                         if (!(r <= gate)) {
                             const bool r_nan = r != r;
                             if (worst < 0 || (!worst_nan && (r_nan || r > worst_r))) {
@@ -697,13 +735,7 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
                 vw[worst] = -1;
                 ext_cost[row * n_ext + (worst - 3)] = INFINITY;
                 double out[3];
-                switch (__builtin_popcount(mask)) {
-                    case 3: extend_dlt<3>(proj_s, pts, co_s, vw, mask, out); break;
-                    case 4: extend_dlt<4>(proj_s, pts, co_s, vw, mask, out); break;
-                    case 5: extend_dlt<5>(proj_s, pts, co_s, vw, mask, out); break;
-                    case 6: extend_dlt<6>(proj_s, pts, co_s, vw, mask, out); break;
-                    default: extend_dlt<7>(proj_s, pts, co_s, vw, mask, out); break;
-                }
+                mask_dlt<3, 7>(proj_s, pts, co_s, vw, mask, out);     // V = 8 cannot follow a drop
                 X0 = out[0], X1 = out[1], X2 = out[2];
             }
             if (dropped) {
@@ -719,14 +751,13 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
 // --------------------------------------------- point refinement ----
 // mvm_refine_points: per match, a damped Gauss-Newton descent
 // of the summed squared reprojection error from the DLT point, and the inverse
-// of the normal matrix at the result.  The shape of prune_views_kernel: one
-// wave per capture (its index a scalar, so the capture's P is read through
-// uniform addresses), four captures per workgroup, lanes striding over the
-// capture's matches; no LDS, no barrier.  The kept set is a bit mask and the
-// view loop runs over compile-time camera slots under the mask's bit, so no
-// register array is indexed by a runtime value.  Every product, sum, division
-// and square root is rounded on its own (this file's fp contract(off)), in
-// the order of tests/refine_model.py, whose bits the kernel returns.
+// of the normal matrix at the result.  One wave per capture (wave_item), so
+// the capture's P is read through uniform addresses.  The kept set is the bit
+// mask of kept_views and the view loop runs over compile-time camera slots
+// under the mask's bit, so no register array is indexed by a runtime value.
+// Every product, sum, division and square root is rounded on its own (this
+// file's fp contract(off)), in the order of tests/refine_model.py, whose bits
+// the kernel returns.
 struct RefineSums {
     double cost, A[6], g[3];     // A: A00 A01 A02 A11 A12 A22
 };
@@ -747,10 +778,8 @@ __device__ __forceinline__ void refine_sums(const double *proj_s, uint32_t mask,
     for (int c = 0; c < MVM_MAX_CAMS; ++c) {
         if ((mask >> c) & 1u) {
             const double *p = proj_s + 12 * c;
-            const double h0 = ((p[0] * X0 + p[1] * X1) + p[2] * X2) + p[3];
-            const double h1 = ((p[4] * X0 + p[5] * X1) + p[6] * X2) + p[7];
-            const double h2 = ((p[8] * X0 + p[9] * X1) + p[10] * X2) + p[11];
-            const double u = h0 / h2, v = h1 / h2;
+            const Homog h = project(p, X0, X1, X2);
+            const double h2 = h.h2, u = h.h0 / h2, v = h.h1 / h2;
             const double ru = u - cx[c], rv = v - cy[c];
             e.cost = e.cost + (ru * ru + rv * rv);
             const double a0 = (p[0] - u * p[8]) / h2, a1 = (p[1] - u * p[9]) / h2,
@@ -794,38 +823,21 @@ __global__ __launch_bounds__(kCompactThreads) void refine_points_kernel(
     const double *__restrict__ proj, const int32_t *__restrict__ views, const double *__restrict__ X,
     int32_t n_scenes, int32_t n_cams, int32_t max_evals, double *__restrict__ X_out,
     double *__restrict__ rms, int32_t *__restrict__ info, double *__restrict__ cov) {
-    const int lane = threadIdx.x % 64;
-    const int64_t s = (int64_t)blockIdx.x * kCompactScenes +
-                      __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-    if (s >= n_scenes) return;
-    const int64_t mo = match_offs[s];
-    const int64_t n = min<int64_t>(count[s], match_offs[s + 1] - mo);
-    const int64_t *co_s = cam_offs + s * n_cams;     // cam_offs holds C S + 1 entries
+    int lane;
+    const int64_t s = wave_item(n_scenes, lane);
+    if (s < 0) return;
+    const auto [mo, n] = match_range(match_offs, count, s);
+    const int64_t *co_s = cam_offs + s * n_cams;
     const double *proj_s = proj + s * n_cams * 12;
     const double qnan = __builtin_nan("");
     for (int64_t w = lane; w < n; w += 64) {
         const int64_t row = mo + w;
         const double Xi0 = X[3 * row], Xi1 = X[3 * row + 1], Xi2 = X[3 * row + 2];
-        // the kept views; an entry that is no detection of its view skips the
-        // row: no index is used unchecked
-        uint32_t mask = 0u;
-        bool ok = true;
+        // an entry that is no detection of its view skips the row (status 3)
+        bool ok;
+        const uint32_t mask = kept_views(views + row * n_cams, co_s, n_cams, ok);
         double cx[MVM_MAX_CAMS], cy[MVM_MAX_CAMS];
-#pragma unroll
-        for (int c = 0; c < MVM_MAX_CAMS; ++c) {
-            if (c < n_cams) {
-                const int32_t v = views[row * n_cams + c];
-                if (v >= 0) {
-                    if (v < co_s[c + 1] - co_s[c]) {
-                        mask |= 1u << c;
-                        cx[c] = pts[2 * (co_s[c] + v)];
-                        cy[c] = pts[2 * (co_s[c] + v) + 1];
-                    } else {
-                        ok = false;
-                    }
-                }
-            }
-        }
+        gather_centroids(pts, co_s, views + row * n_cams, mask, cx, cy);
         const int kept = __builtin_popcount(mask);
         double X0 = Xi0, X1 = Xi1, X2 = Xi2, rms0 = qnan, rms1 = qnan;
         int32_t status = 3, evals = 0;
@@ -1121,17 +1133,15 @@ __global__ __launch_bounds__(kMarkThreads) void mark_used_kernel(
     used[k] = 1;
 }
 
-// One wave per (capture, slot), four to a workgroup (its index a scalar): the
-// leftovers of camera pi[q], counted by ballot + popcount over 64-detection
-// chunks -- the walk of leftover_gather_kernel, so the two agree on every
-// view by construction.  No LDS, no barrier.
+// One wave per (capture, slot) (wave_item): the leftovers of camera pi[q],
+// counted by ballot + popcount over 64-detection chunks -- the walk of
+// leftover_gather_kernel, so the two agree on every view by construction.
 __global__ __launch_bounds__(kCompactThreads) void leftover_count_kernel(
     const int32_t *__restrict__ used, const int64_t *__restrict__ cam_offs, int64_t n_views,
     int32_t n_cams, uint32_t order, int32_t *__restrict__ counts) {
-    const int lane = threadIdx.x % 64;
-    const int64_t sq = (int64_t)blockIdx.x * kCompactScenes +
-                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-    if (sq >= n_views) return;
+    int lane;
+    const int64_t sq = wave_item(n_views, lane);
+    if (sq < 0) return;
     const int64_t s = sq / n_cams;
     const int c = order_cam(order, (int)(sq - s * n_cams));
     const int64_t b = cam_offs[s * n_cams + c], e = cam_offs[s * n_cams + c + 1];
@@ -1146,19 +1156,17 @@ __global__ __launch_bounds__(kCompactThreads) void leftover_count_kernel(
 // The same wave per (capture, slot): leftover l of the chunk goes to row
 // sub_offs[s C + q] + base + (leftovers of the chunk in lower lanes), `base`
 // the scalar count of the chunks before -- input order is kept.  A row is a
-// 16-byte centroid, a 16-byte box and the detection's index in its original
-// view.  Never more rows than sub_offs leaves the view.  VEC: 16-byte
-// accesses (every base 16-byte aligned).
+// detection (load / store_detection<VEC>) and its index in its original
+// view.  Never more rows than sub_offs leaves the view.
 template <bool VEC>
 __global__ __launch_bounds__(kCompactThreads) void leftover_gather_kernel(
     const int32_t *__restrict__ used, const double *__restrict__ pts,
     const int32_t *__restrict__ boxes, const int64_t *__restrict__ cam_offs,
     const int64_t *__restrict__ sub_offs, int64_t n_views, int32_t n_cams, uint32_t order,
     double *__restrict__ pts_out, int32_t *__restrict__ boxes_out, int32_t *__restrict__ orig_out) {
-    const int lane = threadIdx.x % 64;
-    const int64_t sq = (int64_t)blockIdx.x * kCompactScenes +
-                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
-    if (sq >= n_views) return;
+    int lane;
+    const int64_t sq = wave_item(n_views, lane);
+    if (sq < 0) return;
     const int64_t s = sq / n_cams;
     const int c = order_cam(order, (int)(sq - s * n_cams));
     const int64_t b = cam_offs[s * n_cams + c], e = cam_offs[s * n_cams + c + 1];
@@ -1171,15 +1179,7 @@ __global__ __launch_bounds__(kCompactThreads) void leftover_gather_kernel(
         const int64_t pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
         if (keep && pos < room) {
             const int64_t r = dst + pos;
-            if (VEC) {
-                reinterpret_cast<double2 *>(pts_out)[r] = reinterpret_cast<const double2 *>(pts)[k];
-                reinterpret_cast<int4 *>(boxes_out)[r] = reinterpret_cast<const int4 *>(boxes)[k];
-            } else {
-                pts_out[2 * r] = pts[2 * k];
-                pts_out[2 * r + 1] = pts[2 * k + 1];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) boxes_out[4 * r + j] = boxes[4 * k + j];
-            }
+            store_detection<VEC>(boxes_out, pts_out, r, load_detection<VEC>(boxes, pts, k));
             orig_out[r] = (int32_t)(k - b);
         }
         base += __builtin_popcountll(m);
@@ -1193,13 +1193,30 @@ bool aligned16(const T *...p) {
     return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
 }
 
+// What an entry point over a batch of captures opens with.  false: `st` is its
+// return value -- the refusal of a negative n_scenes, or MVM_OK for no capture.
+bool some_captures(int32_t n_scenes, int &st) {
+    mvm_clear_error();
+    st = n_scenes < 0 ? mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes") : MVM_OK;
+    return n_scenes > 0;
+}
+
+// MVM_OK, or the refusal of n_cams outside [lo, MVM_MAX_CAMS]
+int cams_within(int32_t n_cams, int32_t lo) {
+    if (n_cams < lo || n_cams > MVM_MAX_CAMS)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [%d, %d]", n_cams, lo, MVM_MAX_CAMS);
+    return MVM_OK;
+}
+
+// workgroups of a wave-per-item launch (wave_item)
+int64_t wave_grid(int64_t n_items) { return (n_items + kCompactScenes - 1) / kCompactScenes; }
+
 // The camera order of a seed pass, packed as the leftover kernels read it:
 // (a, b, c), then the other cameras ascending.  MVM_OK, or the refusal of
 // n_cams outside 4..MVM_MAX_CAMS or of a triple that is not three distinct
 // cameras < n_cams.
 int leftover_order(int32_t n_cams, int32_t a, int32_t b, int32_t c, uint32_t &order) {
-    if (n_cams < 4 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [4, %d]", n_cams, MVM_MAX_CAMS);
+    if (const int st = cams_within(n_cams, 4)) return st;
     const int32_t seed[3] = {a, b, c};
     for (int k = 0; k < 3; ++k)
         if (seed[k] < 0 || seed[k] >= n_cams)
@@ -1214,10 +1231,14 @@ int leftover_order(int32_t n_cams, int32_t a, int32_t b, int32_t c, uint32_t &or
     return MVM_OK;
 }
 
-// workgroups of a wave per (capture, slot) launch, or -1 beyond one launch
-int64_t leftover_grid(int32_t n_scenes, int32_t n_cams) {
-    const int64_t grid = ((int64_t)n_scenes * n_cams + kCompactScenes - 1) / kCompactScenes;
-    return grid > kMaxGridBlocks ? -1 : grid;
+// workgroups of a wave per (capture, slot) launch: MVM_OK, or the refusal beyond one launch
+int leftover_grid(int32_t n_scenes, int32_t n_cams, unsigned &grid) {
+    const int64_t g = wave_grid((int64_t)n_scenes * n_cams);
+    grid = (unsigned)g;
+    if (g > kMaxGridBlocks)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more views than one launch holds; split them",
+                        n_scenes);
+    return MVM_OK;
 }
 
 }  // namespace
@@ -1227,11 +1248,9 @@ extern "C" {
 int mvm_rig_matrices(const float *K_dev, const double *RT_dev, const int32_t *pair_a,
                      const int32_t *pair_b, int32_t n_scenes, int32_t n_cams, int32_t n_pairs,
                      double *F_dev, double *proj_dev, int32_t *status_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
-    if (n_cams < 2 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [2, %d]", n_cams, MVM_MAX_CAMS);
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
+    if ((rc = cams_within(n_cams, 2))) return rc;
     if (n_pairs < 1 || n_pairs > MVM_MAX_PAIRS)
         return mvm_fail(MVM_ERR_UNSUPPORTED, "n_pairs=%d outside [1, %d]", n_pairs, MVM_MAX_PAIRS);
     if (const int st = mvm_require_ptrs({{K_dev, "K_dev"},   {RT_dev, "RT_dev"}, {pair_a, "pair_a"},
@@ -1263,9 +1282,8 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
                         int32_t scene_base, int64_t *dense_offs_dev, int32_t *scene_out_dev,
                         int32_t *match_out_dev, float *cost_out_dev, double *X_out_dev,
                         int32_t *boxes_out_dev, double *cent_out_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
     if (const int st = mvm_require_ptrs({{match_dev, "match_dev"},         {cost_dev, "cost_dev"},
                                          {X_dev, "X_dev"},                 {count_dev, "count_dev"},
                                          {seg_offs_dev, "seg_offs_dev"},   {pts_dev, "pts_dev"},
@@ -1277,7 +1295,7 @@ int mvm_compact_matches(const int32_t *match_dev, const float *cost_dev, const d
         return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
-    const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
+    const int grid = (int)wave_grid(n_scenes);
     dispatch_bool(aligned16(pts_dev, boxes_dev, boxes_out_dev, cent_out_dev), [&](auto vec) {
         compact_matches_kernel<decltype(vec)::value><<<grid, kCompactThreads, 0, s>>>(
             match_dev, cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev, boxes_dev,
@@ -1296,11 +1314,9 @@ int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
                               int32_t *views_out_dev, int32_t *n_views_out_dev, float *cost_out_dev,
                               float *ext_cost_out_dev, double *X_out_dev, int32_t *boxes_out_dev,
                               double *cent_out_dev, double *reproj_out_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
-    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
+    if ((rc = cams_within(n_cams, 3))) return rc;
     const bool ext = n_cams > 3;         // no extra view: the [cap, 0] arrays may be NULL
     if (const int st = mvm_require_ptrs({{views_dev, "views_dev"},
                                          {cost_dev, "cost_dev"},
@@ -1325,7 +1341,7 @@ int mvm_compact_matches_views(const int32_t *views_dev, const float *cost_dev,
         return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     pack_scan_kernel<<<1, 1024, 0, s>>>(count_dev, n_scenes, dense_offs_dev);
-    const int grid = (n_scenes + kCompactScenes - 1) / kCompactScenes;
+    const int grid = (int)wave_grid(n_scenes);
     dispatch_bool(aligned16(pts_dev, boxes_dev, boxes_out_dev, cent_out_dev), [&](auto vec) {
         compact_matches_views_kernel<decltype(vec)::value><<<grid, kCompactThreads, 0, s>>>(
             views_dev, cost_dev, ext_cost_dev, X_dev, count_dev, seg_offs_dev, dense_offs_dev, pts_dev,
@@ -1341,11 +1357,9 @@ int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *co
                                 const int64_t *cam_offs_dev, const double *proj_dev, double gate,
                                 int32_t *views_dev, float *ext_cost_dev, double *X_dev,
                                 int32_t *pruned_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
-    if (n_cams < 4 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [4, %d]", n_cams, MVM_MAX_CAMS);
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
+    if ((rc = cams_within(n_cams, 4))) return rc;
     if (!(gate >= 0.0))                  // NaN included
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "gate=%g: a number >= 0 (or +inf) required", gate);
     if (const int st = mvm_require_ptrs({{match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
@@ -1354,7 +1368,7 @@ int mvm_prune_views_triangulate(const int64_t *match_offs_dev, const int32_t *co
                                          {ext_cost_dev, "ext_cost_dev"},     {X_dev, "X_dev"},
                                          {pruned_dev, "pruned_dev"}}))
         return st;
-    const int grid = (int)(((int64_t)n_scenes + kCompactScenes - 1) / kCompactScenes);
+    const int grid = (int)wave_grid(n_scenes);
     prune_views_kernel<<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
         match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, gate, n_scenes, n_cams, views_dev,
         ext_cost_dev, X_dev, pruned_dev);
@@ -1366,11 +1380,9 @@ int mvm_refine_points(const int64_t *match_offs_dev, const int32_t *count_dev, i
                       const double *proj_dev, const int32_t *views_dev, const double *X_dev,
                       int32_t max_evals, double *X_out_dev, double *rms_dev, int32_t *info_dev,
                       double *cov_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
-    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
+    if ((rc = cams_within(n_cams, 3))) return rc;
     if (max_evals < 1 || max_evals > 64)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "max_evals=%d outside [1, 64]", max_evals);
     if (const int st = mvm_require_ptrs({{match_offs_dev, "match_offs_dev"}, {count_dev, "count_dev"},
@@ -1379,7 +1391,7 @@ int mvm_refine_points(const int64_t *match_offs_dev, const int32_t *count_dev, i
                                          {X_dev, "X_dev"},                   {X_out_dev, "X_out_dev"},
                                          {rms_dev, "rms_dev"},               {info_dev, "info_dev"}}))
         return st;                       // cov_dev may be NULL: no covariance is written
-    const int grid = (int)(((int64_t)n_scenes + kCompactScenes - 1) / kCompactScenes);
+    const int grid = (int)wave_grid(n_scenes);
     refine_points_kernel<<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
         match_offs_dev, count_dev, pts_dev, cam_offs_dev, proj_dev, views_dev, X_dev, n_scenes, n_cams,
         max_evals, X_out_dev, rms_dev, info_dev, cov_dev);
@@ -1390,9 +1402,8 @@ int mvm_mark_used(const int32_t *views_dev, const int64_t *match_offs_dev, const
                   int64_t n_rows, int32_t n_scenes, int32_t n_cams, int32_t seed_a, int32_t seed_b,
                   int32_t seed_c, const int64_t *sub_cam_offs_dev, const int32_t *orig_dev,
                   const int64_t *cam_offs_dev, int64_t n_det, int32_t *used_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
     if (n_rows < 0 || n_det < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_rows or n_det");
     uint32_t order = 0;
     if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
@@ -1418,19 +1429,16 @@ int mvm_mark_used(const int32_t *views_dev, const int64_t *match_offs_dev, const
 int mvm_leftover_counts(const int32_t *used_dev, const int64_t *cam_offs_dev, int32_t n_scenes,
                         int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
                         int32_t *counts_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
     uint32_t order = 0;
     if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
     if (const int st = mvm_require_ptrs(
             {{used_dev, "used_dev"}, {cam_offs_dev, "cam_offs_dev"}, {counts_dev, "counts_dev"}}))
         return st;
-    const int64_t grid = leftover_grid(n_scenes, n_cams);
-    if (grid < 0)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more views than one launch holds; split them",
-                        n_scenes);
-    leftover_count_kernel<<<(unsigned)grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+    unsigned grid;
+    if ((rc = leftover_grid(n_scenes, n_cams, grid))) return rc;
+    leftover_count_kernel<<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
         used_dev, cam_offs_dev, (int64_t)n_scenes * n_cams, n_cams, order, counts_dev);
     return mvm_check_launch("leftover_count_kernel");
 }
@@ -1440,9 +1448,8 @@ int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const in
                         int32_t n_cams, int32_t seed_a, int32_t seed_b, int32_t seed_c,
                         double *pts_out_dev, int32_t *boxes_out_dev, int32_t *orig_out_dev,
                         mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
     uint32_t order = 0;
     if (const int st = leftover_order(n_cams, seed_a, seed_b, seed_c, order)) return st;
     if (const int st = mvm_require_ptrs({{used_dev, "used_dev"},
@@ -1454,13 +1461,11 @@ int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const in
                                          {boxes_out_dev, "boxes_out_dev"},
                                          {orig_out_dev, "orig_out_dev"}}))
         return st;
-    const int64_t grid = leftover_grid(n_scenes, n_cams);
-    if (grid < 0)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_scenes=%d: more views than one launch holds; split them",
-                        n_scenes);
+    unsigned grid;
+    if ((rc = leftover_grid(n_scenes, n_cams, grid))) return rc;
     dispatch_bool(aligned16(pts_dev, boxes_dev, pts_out_dev, boxes_out_dev), [&](auto vec) {
         leftover_gather_kernel<decltype(vec)::value>
-            <<<(unsigned)grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+            <<<grid, kCompactThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
                 used_dev, pts_dev, boxes_dev, cam_offs_dev, sub_cam_offs_dev, (int64_t)n_scenes * n_cams,
                 n_cams, order, pts_out_dev, boxes_out_dev, orig_out_dev);
     });
@@ -1500,15 +1505,10 @@ int mvm_triangulate_dlt(const double *proj_dev, const int32_t *set_of_point_dev,
     if (n_points == 0) return MVM_OK;
     if (!proj_dev || !pts2d_dev || !X_dev) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (n_views) {
-        case 2: launch_dlt<2>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        case 3: launch_dlt<3>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        case 4: launch_dlt<4>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        case 5: launch_dlt<5>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        case 6: launch_dlt<6>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        case 7: launch_dlt<7>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-        default: launch_dlt<8>(proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev, s); break;
-    }
+    dispatch_int<2, 3, 4, 5, 6, 7, 8>(n_views, [&](auto nv) {
+        dlt_kernel<decltype(nv)::value><<<(n_points + 255) / 256, 256, 0, s>>>(
+            proj_dev, set_of_point_dev, pts2d_dev, n_points, X_dev);
+    });
     return mvm_check_launch("dlt_kernel");
 }
 
@@ -1518,9 +1518,8 @@ int mvm_select_triangulate(const float *cube_dev, const int64_t *cube_offs_dev,
                            const double *pts_dev, const double *proj_dev, int32_t n_scenes,
                            double threshold, int32_t *match_dev, float *cost_dev, double *X_dev,
                            int32_t *count_dev, mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_scenes == 0) return MVM_OK;
+    int rc;
+    if (!some_captures(n_scenes, rc)) return rc;
     if (!cube_offs_dev || !cam_offs_dev || !lsap_out_offs_dev || !proj_dev || !count_dev)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "null pointer");
     select_triangulate_kernel<<<n_scenes, kSelThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
@@ -1539,8 +1538,7 @@ int mvm_extend_select_triangulate(const float *E_dev, const int64_t *ext_offs_de
                                   double *X_dev, mvm_stream_t stream) {
     mvm_clear_error();
     if (n_scenes < 0) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative n_scenes");
-    if (n_cams < 3 || n_cams > MVM_MAX_CAMS)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_cams=%d outside [3, %d]", n_cams, MVM_MAX_CAMS);
+    if (const int st = cams_within(n_cams, 3)) return st;      // refused for an empty batch too
     if (n_scenes == 0 || n_cams == 3) return MVM_OK;
     // E / row_ind / col_ind / pts may be NULL when every extra view or every
     // capture is empty (nothing then reads them)

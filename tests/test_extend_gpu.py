@@ -304,7 +304,9 @@ class SelBatch:
                         views[mo + r, 3 + e], ext[mo + r, e] = l, Ed[r, l]
             for w in range(n):
                 cams = np.nonzero(views[mo + w] >= 0)[0]
-                if cams.size > 3:
+                # a seed that is no detection of its view: the X that came in stands
+                seeds = all(0 <= views[mo + w, c] < self.counts[s, c] for c in range(3))
+                if cams.size > 3 and seeds:
                     kept[mo + w] = True
                     p = np.stack([self.view(s, c)[views[mo + w, c]] for c in cams])
                     X[mo + w] = OP.triangulate(self.proj[s, cams][None], p[None])[0]
@@ -395,6 +397,35 @@ def test_extend_select_ignores_pairs_that_are_no_indices(cuda):
     b.col_ind[3] = 8
     views, ext, X = b.run(cuda, 30.0)
     assert (views[:6, 3] >= 0).sum() == 2
+
+
+def test_extend_select_seed_that_is_no_detection_of_its_view(cuda):
+    """One capture, C = 4, views of (3, 3, 3, 2) detections, three matches:
+    row 1's seed in view 1 is 3 (the view's size), row 2's seed in view 0 is
+    -1.  Every row is assigned an extra view under the threshold -- the
+    two-detection view 3 holds two pairs a launch, so row 0 goes with row 1 in
+    one launch and with row 2 in the next.  views and ext_cost are set as for
+    any row; the X of rows 1 and 2 keeps the bits it came with (distinct finite
+    sentinels) and row 0's is the four-view DLT."""
+    b = SelBatch(31, 4, [3], [(2,)], lambda s, e, m, rng: np.float32(1.0))
+    assert b.counts.tolist() == [[3, 3, 3, 2]]
+    # row 0's detection in view 3: its three-view point seen by camera 3
+    h = b.proj[0, 3] @ np.append(b.X0[0], 1.0)
+    b.view(0, 3)[0] = np.round(h[:2] / h[2] * 2) / 2
+    b.E[:] = np.float32(1.0)
+    b.match[1, 1] = 3
+    b.match[2, 0] = -1
+    sent = np.arange(1.0, 1.0 + b.X0.size).reshape(b.X0.shape) * 1.25
+    b.X0[:] = sent
+    for bad in (1, 2):
+        b.row_ind[:], b.col_ind[:] = [0, bad], [0, 1]
+        views, kept = b.check(cuda, 30.0)
+        assert kept.tolist() == [True, False, False, False, False]
+        assert views[:3, 3].tolist() == [[0, 1, -1], [0, -1, 1]][bad - 1]
+        assert np.array_equal(views[:3, :3], b.match[:3])
+        X = b.run(cuda, 30.0)[2]
+        assert np.array_equal(X[1:].view(np.uint64), sent[1:].view(np.uint64))
+        assert np.isfinite(X[0]).all() and not np.array_equal(X[0], sent[0])
 
 
 # ----------------------------------------------------------- end to end ----

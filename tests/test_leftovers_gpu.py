@@ -160,6 +160,55 @@ def test_marking_the_matches_of_a_later_pass(cuda, C, seed):
     _check_leftovers(c, want, seed, cuda)
 
 
+def test_rows_off_16_byte_alignment(cuda):
+    """pts / boxes, and separately pts_out / boxes_out, one element into their
+    allocations (test_view_table_gpu's construction): the gather without the
+    16-byte accesses writes the aligned run's bytes and leaves the rows behind
+    them alone.  Views of 0, 1, 63, 64 and 65 detections, half of them used."""
+    C, S, seed = 4, 2, (1, 0, 3)
+    rng = np.random.default_rng(41)
+    sizes = np.array([[0, 1, 63, 64], [65, 64, 1, 63]], np.int64)
+    cam_offs = np.zeros(S * C + 1, np.int64)
+    np.cumsum(sizes.reshape(-1), out=cam_offs[1:])
+    n = int(cam_offs[-1])
+    pts_h = rng.integers(0, 4800, (n, 2)).astype(np.float64) / 2
+    boxes_h = rng.integers(-50, 2500, (n, 4)).astype(np.int32)
+    used_h = (rng.random(n) < 0.5).astype(np.int32)
+    w_pts, w_boxes, w_orig, sub_offs = M.leftover_gather(used_h, pts_h, boxes_h, cam_offs, C,
+                                                        M.seed_order(seed, C))
+    m = int(sub_offs[-1])
+    assert n // 3 < m < 2 * n // 3
+
+    def shifted(t):
+        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=cuda)
+        buf[1:] = t.reshape(-1)
+        return buf[1:].view(t.shape)
+
+    def run(shift_in, shift_out):
+        pts, boxes = _t(pts_h, cuda), _t(boxes_h, cuda)
+        outs = [torch.full((m + TAIL, 2), -1.25, dtype=torch.float64, device=cuda),
+                torch.full((m + TAIL, 4), FILL, dtype=torch.int32, device=cuda),
+                torch.full((m + TAIL,), FILL, dtype=torch.int32, device=cuda)]
+        if shift_in:
+            pts, boxes = shifted(pts), shifted(boxes)
+        if shift_out:
+            outs[:2] = [shifted(t) for t in outs[:2]]
+        assert (pts.data_ptr() % 16, boxes.data_ptr() % 16) == ((8, 4) if shift_in else (0, 0))
+        assert (outs[0].data_ptr() % 16, outs[1].data_ptr() % 16) == ((8, 4) if shift_out else (0, 0))
+        torch.ops.mvmatch_views.leftover_gather_out(_t(used_h, cuda), pts, boxes, _t(cam_offs, cuda),
+                                                    _t(sub_offs, cuda), C, list(seed), *outs)
+        return [t.cpu().numpy() for t in outs]
+
+    aligned = run(False, False)
+    tail = lambda a, v: np.concatenate([a, np.full((TAIL,) + a.shape[1:], v, a.dtype)])
+    assert np.array_equal(aligned[0].view(np.int64), tail(w_pts, -1.25).view(np.int64))
+    assert np.array_equal(aligned[1], tail(w_boxes, FILL)) and np.array_equal(aligned[2], tail(w_orig, FILL))
+    for shift in ((True, False), (False, True)):
+        got = run(*shift)
+        assert np.array_equal(got[0].view(np.int64), aligned[0].view(np.int64)), shift
+        assert np.array_equal(got[1], aligned[1]) and np.array_equal(got[2], aligned[2]), shift
+
+
 def test_wrappers_validate(cuda):
     c = case(5, 4, "last")
     a = dict(views=_t(c.views, cuda), match_offs=_t(c.match_offs, cuda), count=_t(c.count, cuda),
