@@ -842,6 +842,10 @@ int mvm_leftover_gather(const int32_t *used_dev, const double *pts_dev, const in
  *   cov_dev   f64 [.., 6]   may be NULL; the upper triangle, row-major, of the
  *             inverse of the undamped A at X_out (mm^2 / px^2: times the
  *             caller's pixel variance), NaN where a pivot is not > 0.
+ * Status 2 after accepted steps undoes them: X_out = X, rms[1] = rms[0], cov
+ * is that of the A at X, and the count keeps the trial costs evaluated until
+ * then.  Status 1 met after rejected steps returns the last accepted point
+ * with the count at max_evals.
  * Only the count_dev[s] rows of every capture are written.  X_out_dev must not
  * overlap X_dev.  One launch on `stream`, a wave per capture; no allocation,
  * copy or synchronisation.  n_scenes == 0 launches nothing.  A NULL pointer

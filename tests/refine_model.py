@@ -33,6 +33,12 @@ CONVERGED, CAPPED, FAILED, SKIPPED = 0, 1, 2, 3
 NAN = float("nan")
 
 
+def _note(trace, key, value):
+    """Record ``value`` under ``key`` where a trace is kept (refine_trace) -> None."""
+    if trace is not None:
+        trace[key] = value
+
+
 def _div(a, b):
     """IEEE a / b."""
     if b != 0.0:
@@ -82,34 +88,34 @@ def normal_equations(P, cent, X):
     return A, g
 
 
-def ldlt(M):
+def ldlt(M, trace=None):
     """M = L D L^T of the symmetric [M00, M01, M02, M11, M12, M22] in this
     order -> (d0, d1, d2, l10, l20, l21), or None at the first pivot that is
-    not > 0 (a NaN is not)."""
+    not > 0 (a NaN is not); ``trace["pivot"]`` then names it (0, 1, 2)."""
     M00, M01, M02, M11, M12, M22 = M
     d0 = M00
     if not d0 > 0.0:
-        return None
+        return _note(trace, "pivot", 0)
     l10 = M01 / d0
     l20 = M02 / d0
     d1 = M11 - l10 * M01
     if not d1 > 0.0:
-        return None
+        return _note(trace, "pivot", 1)
     t = M12 - l20 * M01
     l21 = t / d1
     d2 = (M22 - l20 * M02) - l21 * t
     if not d2 > 0.0:
-        return None
+        return _note(trace, "pivot", 2)
     return d0, d1, d2, l10, l20, l21
 
 
-def solve(A, g, lam):
+def solve(A, g, lam, trace=None):
     """delta of (A + lam diag A) delta = -g, or None where a pivot fails."""
     M = list(A)
     M[0] = A[0] + lam * A[0]
     M[3] = A[3] + lam * A[3]
     M[5] = A[5] + lam * A[5]
-    f = ldlt(M)
+    f = ldlt(M, trace)
     if f is None:
         return None
     d0, d1, d2, l10, l20, l21 = f
@@ -152,51 +158,96 @@ def _finite(*vals):
     return all(math.isfinite(x) for x in vals)
 
 
-def refine_row(P, cent, X, max_evals):
+TRACE_KEYS = ("evals", "accepted", "rejections", "longest_run", "ties", "nan_trials", "inf_trials", "floor_steps",
+              "xx_zero")
+
+
+def refine_row(P, cent, X, max_evals, trace=None):
     """The definition for one row that is not skipped: P / cent of its kept
     views in ascending camera order, X its start.
-    -> (X_out [3], rms [2], status, evals, cov [6])."""
+    -> (X_out [3], rms [2], status, evals, cov [6]).
+    ``trace``: a dict that receives what the descent did (``refine_trace``);
+    it takes no part in any value returned."""
     X_in = [float(x) for x in X]
     X = list(X_in)
     n = float(len(P))
     cost0 = c = cost(P, cent, X)
     lam, evals, status = LAMBDA0, 0, None
+    t = trace
+    run = 0                                  # the rejections since the last accepted step (traced only)
+    if t is not None:
+        t.update(dict.fromkeys(TRACE_KEYS, 0), pivot=None, failed_at=None, failed_after_accept=False,
+                 capped_in_run=False)
     if not _finite(c):
         status = FAILED
+        _note(t, "failed_at", "start")
     while status is None:
         A, g = normal_equations(P, cent, X)
         if not _finite(*A, *g):
             status = FAILED
+            _note(t, "failed_at", "sums")
             break
         while True:
-            d = solve(A, g, lam)
+            d = solve(A, g, lam, t)
             if d is None or not _finite(*d):
                 status = FAILED
+                _note(t, "failed_at", "pivot" if d is None else "step")
                 break
+            if t is not None and (X[0] * X[0] + X[1] * X[1]) + X[2] * X[2] == 0.0:
+                t["xx_zero"] += 1
             if (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= STEP_TOL * ((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]):
                 status = CONVERGED
                 break
             if evals == max_evals:
                 status = CAPPED
+                _note(t, "capped_in_run", run > 0)
                 break
             evals += 1
             Y = [X[0] + d[0], X[1] + d[1], X[2] + d[2]]
             c1 = cost(P, cent, Y)
+            if t is not None:
+                t["floor_steps"] += lam == LAMBDA_MIN
             if c1 < c:
                 X, c = Y, c1
                 lam = max(lam / FACTOR, LAMBDA_MIN)
+                if t is not None:
+                    t["accepted"] += 1
+                    run = 0
                 break
+            if t is not None:
+                run += 1
+                t["rejections"] += 1
+                t["longest_run"] = max(t["longest_run"], run)
+                t["ties"] += c1 == c
+                t["nan_trials"] += c1 != c1
+                t["inf_trials"] += c1 == math.inf
             lam = lam * FACTOR
     if status == FAILED:
+        _note(t, "failed_after_accept", t is not None and t["accepted"] > 0)
         X, c = X_in, cost0
+    _note(t, "evals", evals)
     rms = [math.sqrt(cost0 / n), math.sqrt(c / n)]
     cov = inverse(normal_equations(P, cent, X)[0])
     return X, rms, status, evals, cov
 
 
-def refine(views, X, match_offs, count, pts, cam_offs, proj, max_evals=10, fill=None):
+def refine_trace(P, cent, X, max_evals):
+    """``refine_row`` and what its descent did -> (its result, trace):
+    ``evals``, ``accepted``, ``rejections`` and the ``longest_run`` of them,
+    rejections whose trial cost equals the current one (``ties``), is NaN
+    (``nan_trials``) or +inf (``inf_trials``), evaluations whose damping is
+    the floor (``floor_steps``), convergence tests with X.X = 0 (``xx_zero``),
+    ``failed_at`` ("start", "sums", "pivot", "step" or None) with the
+    ``pivot`` that failed (0, 1, 2), ``failed_after_accept`` and
+    ``capped_in_run`` (the cap met after a rejection)."""
+    trace = {}
+    return refine_row(P, cent, X, max_evals, trace), trace
+
+
+def refine(views, X, match_offs, count, pts, cam_offs, proj, max_evals=10, fill=None, traces=None):
     """The op over a batch.  ``fill``: what the outputs hold before the call,
     (X_out, rms, info, cov) arrays, copied (default: NaN / INT32_MIN).
+    ``traces``: a dict that receives {row: trace} of the rows not skipped.
     -> (X_out f64 [cap, 3], rms f64 [cap, 2], info int32 [cap, 2], cov f64 [cap, 6])."""
     cap, C = views.shape
     if fill is None:
@@ -216,7 +267,8 @@ def refine(views, X, match_offs, count, pts, cam_offs, proj, max_evals=10, fill=
                 continue
             P = [proj[s, d].tolist() for d in K]
             cent = [pts[co[d] + v[d]].tolist() for d in K]
-            x, r, status, evals, cv = refine_row(P, cent, X[row], max_evals)
+            trace = None if traces is None else traces.setdefault(row, {})
+            x, r, status, evals, cv = refine_row(P, cent, X[row], max_evals, trace)
             X_out[row], rms[row], info[row], cov[row] = x, r, (status, evals), cv
     return X_out, rms, info, cov
 
@@ -355,6 +407,9 @@ def case(name, C):
                      bad_rows=((2, 1), (2, 6), (2, 10)), single_rows=((2, 0), (2, 3), (2, 8)))
     if name == "truth":         # 600 rigs, one noisy point each over all its views (the mean distance to the truth)
         return build(C, (1,) * 600, (1,) * 600, 2000 + C, exact_every=0, full_views=True)
+    import refine_edges                 # where the descent rejects, stalls and fails (imports this module)
+    if name in refine_edges.NAMES:
+        return refine_edges.build(name, C)
     raise KeyError(name)
 
 

@@ -68,7 +68,7 @@ def test_model_returns_scipys_minimiser(C):
 @pytest.mark.parametrize("max_evals", M.MAX_EVALS)
 @pytest.mark.parametrize("C", M.CAMS)
 def test_cost_never_rises_and_rms_matches(C, max_evals):
-    for name in ("counts", "regimes"):
+    for name in ("counts", "regimes", "far", "origin", "centres", "neardup", "flat", "mixed", "scaled"):
         c = M.case(name, C)
         X_out, rms, info, cov = M.expected(name, C, max_evals)
         for r in c.rows():
