@@ -206,6 +206,12 @@ SIGNATURES = {
         _vp, _vp, _i32, _i32,               # match_offs, count, n_scenes, n_cams
         _vp, _vp, _vp, _vp, _vp, _i32,      # pts, cam_offs, proj, views, X, max_evals
         _vp, _vp, _vp, _vp, _vp]),          # X_out, rms, info, cov (may be NULL) (out), stream
+    "mvm_crop_views": (ctypes.c_int, [
+        _vp, _i32, _i32, _i32, _i32,        # images, n_scenes, n_cams, img_h, img_w
+        _vp, _i32, _vp, _vp,                # scene, scene_base, views, boxes
+        _i64, _i64, _vp, _i32,              # row0, n_rows, cams (host), n_sel
+        _i32, _i32, _vp, _i32,              # size, fill, lut, out_kind
+        _vp, _vp, _vp]),                    # out, geom (may be NULL) (out), stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

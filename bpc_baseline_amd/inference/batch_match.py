@@ -380,6 +380,24 @@ class MatchTable:
         return [h["reproj"][r][h["views"][r] >= 0]
                 for r in range(int(self.offs[s]), int(self.offs[s + 1]))]
 
+    def crops(self, images: torch.Tensor, rows=None, cams=None, **kw):
+        """The pose head's input crops of the table's views
+        (``ops_views.crop_views`` on the table's own ``scene`` / ``views`` /
+        ``boxes``): ``images`` uint8 [S, n_cams, H, W, 3] (B, G,
+        R) on the device, ``rows`` a (begin, end) pair (default all), ``cams``
+        the cameras wanted (default all), the other keywords ``crop_views``'s
+        (``size``, ``mean``, ``std``, ``fill``, ``dtype``, ``scene_base``: what
+        the table's scene ids start at).  Works on the plain three-camera
+        table, on the view table and on ``table_all()``, whose views and boxes
+        are in original camera order.
+        -> (crops [rows, cams, 3, size, size], geom int32 [rows, cams, 8]).
+        One float32 crop of 256 x 256 is 786 KB, so a caller feeds its head
+        in row ranges, not the whole table at once.  ``cams=(2,)`` is what
+        the reference's ``final_rotation`` uses."""
+        views = self.views if self.views is not None else self.match
+        return ops_views.crop_views(images, self.scene, views, self.boxes, self.n_cams, rows=rows, cams=cams,
+                                    **kw)
+
 
 def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    img_offs: torch.Tensor, Ks: np.ndarray, RTs: np.ndarray, *,

@@ -12,19 +12,27 @@ fake that returns None.
   mvmatch_views::leftover_counts_out   mvm_leftover_counts
   mvmatch_views::leftover_gather_out   mvm_leftover_gather
   mvmatch_views::refine_points_out     mvm_refine_points           (DESIGN §3.17)
+  mvmatch_views::crop_views_out        mvm_crop_views              (DESIGN §3.18)
 """
 from __future__ import annotations
 
+import ctypes
 import math
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from . import _native, ops
-from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64
+from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64, u8
 
-__all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points"]
+__all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points",
+           "norm_lut", "crop_views"]
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # RGB
+CROP_MAX_SIZE, CROP_MAX_IMAGE = 1024, 16384
+_CROP_KINDS = {torch.float32: 0, torch.float16: 1}
 
 
 def _check_gate(gate) -> float:
@@ -189,6 +197,47 @@ def refine_points_out(views: Tensor, X: Tensor, match_offs: Tensor, count: Tenso
               ops._p(rms), ops._p(info), ops._p(cov), ops._stream(views))
 
 
+@ops._gpu_op("crop_views_out", ("out", "geom"), namespace="mvmatch_views")
+def crop_views_out(images: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, n_cams: int, scene_base: int,
+                   row0: int, n_rows: int, cams: List[int], size: int, fill: int, lut: Tensor, out: Tensor,
+                   geom: Optional[Tensor]) -> None:
+    """The crops of rows ``row0 : row0 + n_rows`` in the cameras ``cams``
+    (mvm_crop_views).  ``images`` / ``scene`` / ``views`` / ``boxes`` / ``lut``
+    are read only; ``out`` / ``geom`` (None: not written) out."""
+    dev = ops._gpu(images, "images", "crop kernel")
+    if not 3 <= n_cams <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if images.dim() != 5 or images.shape[1] != n_cams or images.shape[4] != 3:
+        raise ValueError(f"images must be [S, {n_cams}, H, W, 3], got {tuple(images.shape)}")
+    S, H, W = int(images.shape[0]), int(images.shape[2]), int(images.shape[3])
+    if not (1 <= H <= CROP_MAX_IMAGE and 1 <= W <= CROP_MAX_IMAGE):
+        raise ValueError(f"images: expected 1..{CROP_MAX_IMAGE} rows and columns, got {H} x {W}")
+    if not 1 <= size <= CROP_MAX_SIZE:
+        raise ValueError(f"size: expected 1..{CROP_MAX_SIZE}, got {size}")
+    if not 0 <= fill <= 255:
+        raise ValueError(f"fill: expected 0..255, got {fill}")
+    if not 1 <= len(cams) <= n_cams or not all(0 <= c < n_cams for c in cams):
+        raise ValueError(f"cams: expected 1..{n_cams} cameras < {n_cams}, got {list(cams)}")
+    if row0 < 0 or n_rows < 0:
+        raise ValueError(f"rows: expected 0 <= begin <= end, got ({row0}, {row0 + n_rows})")
+    if out.dtype not in _CROP_KINDS:
+        raise ValueError(f"out: expected torch.float32 or torch.float16, got {out.dtype}")
+    n_end, n_slots = row0 + n_rows, n_rows * len(cams)
+    rows = [(images, "images", u8, S * n_cams * H * W * 3, EXACT), (scene, "scene", i32, n_end, AT_LEAST),
+            (views, "views", i32, n_cams * n_end, AT_LEAST), (boxes, "boxes", i32, 4 * n_cams * n_end, AT_LEAST),
+            (lut, "lut", out.dtype, 3 * 256, EXACT), (out, "out", out.dtype, 3 * size * size * n_slots, EXACT)]
+    if geom is not None:
+        rows.append((geom, "geom", i32, 8 * n_slots, EXACT))
+    ops._check_args(dev, rows)
+    if n_rows == 0:
+        return                       # no row: nothing to launch
+    if S == 0:
+        raise ValueError("images holds no capture")
+    ops._call("mvm_crop_views", ops._p(images), S, n_cams, H, W, ops._p(scene), scene_base, ops._p(views),
+              ops._p(boxes), row0, n_rows, (ctypes.c_int32 * len(cams))(*cams), len(cams), size, fill,
+              ops._p(lut), _CROP_KINDS[out.dtype], ops._p(out), ops._p(geom), ops._stream(images))
+
+
 def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
               seed=(0, 1, 2), sub_cam_offs: Optional[Tensor] = None, orig: Optional[Tensor] = None) -> Tensor:
     """Flag the detections the matches of one pass hold (device).
@@ -283,3 +332,70 @@ def refine_points(views: Tensor, X: Tensor, match_offs: Tensor, count: Tensor, p
     torch.ops.mvmatch_views.refine_points_out(views, X, match_offs, count, pts, cam_offs, proj.contiguous(),
                                               int(n_cams), max_evals, X_out, rms, info, cv)
     return X_out, rms, info, cv
+
+
+def norm_lut(mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype: torch.dtype = torch.float32) -> Tensor:
+    """The look-up table of ``crop_views`` (host): float32
+    [3, 256], ``lut[c][v] = (float32(v) / float32(255) - float32(mean[c])) /
+    float32(std[c])`` with one IEEE float32 operation each -- what ``to_tensor``
+    followed by ``normalize`` computes for level v of plane c (``mean`` /
+    ``std`` in plane order: R, G, B).  ``dtype=torch.float16``: that table
+    rounded to nearest-even once."""
+    if dtype not in _CROP_KINDS:
+        raise ValueError(f"dtype: expected torch.float32 or torch.float16, got {dtype}")
+    mean, std = (np.asarray([float(x) for x in v], np.float32) for v in (mean, std))
+    if mean.shape != (3,) or std.shape != (3,):
+        raise ValueError("mean / std: expected three values each (R, G, B)")
+    v = np.arange(256, dtype=np.float32) / np.float32(255)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lut = (v[None, :] - mean[:, None]) / std[:, None]
+    return torch.from_numpy(np.ascontiguousarray(lut, np.float32)).to(dtype)
+
+
+def crop_views(images: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, n_cams: int,
+               rows: Optional[Sequence[int]] = None, cams: Optional[Sequence[int]] = None, size: int = 256,
+               mean=IMAGENET_MEAN, std=IMAGENET_STD, fill: int = 255, dtype: torch.dtype = torch.float32,
+               scene_base: int = 0):
+    """The pose head's input crops of a match table's views (device; DESIGN
+    §3.18).  ``images`` uint8 [S, n_cams, H, W, 3], channel order B, G, R;
+    ``scene`` int32 [n], ``views`` int32 [n, n_cams] (a three-camera table:
+    its ``match``) and ``boxes`` int32 [n, n_cams, 4] a ``MatchTable``'s
+    fields, none written.  For every row of ``rows`` ((begin, end), default
+    all) and every camera of ``cams`` (default all, any order): the row's box
+    in that camera is clipped to the image, resampled by the exact box
+    integral so that its longer side is ``size``, centred on a ``size`` x
+    ``size`` canvas of ``fill`` and sent through the table ``norm_lut(mean,
+    std, dtype)``, R plane first.  tests/crop_model.py states every step; the result is its bits.
+    -> (crops ``dtype`` [rows, cams, 3, size, size]; geom int32 [rows, cams,
+    8]: (status, xa, ya, w, h, new_w, new_h, image index), status 0 made, 1
+    made from a clipped box, 2 empty after clipping, 3 no view (``views <
+    0``), 4 ``scene - scene_base`` is no capture of ``images``; for 2-4 the
+    crop is all fill).  One float32 crop of 256 x 256 is 786 KB: pass row
+    ranges."""
+    n_cams = int(n_cams)
+    n = int(scene.shape[0])
+    if rows is None:
+        rows = (0, n)
+    try:
+        begin, end = (int(r) for r in rows)
+    except (TypeError, ValueError):
+        raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+    if not 0 <= begin <= end <= n:
+        raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+    cams = list(range(n_cams)) if cams is None else [int(c) for c in cams]
+    if isinstance(size, bool) or not isinstance(size, int):
+        raise ValueError(f"size: expected an int in 1..{CROP_MAX_SIZE}, got {size!r}")
+    if isinstance(fill, bool) or not isinstance(fill, int):
+        raise ValueError(f"fill: expected an int in 0..255, got {fill!r}")
+    if dtype not in _CROP_KINDS:
+        raise ValueError(f"dtype: expected torch.float32 or torch.float16, got {dtype}")
+    dev = images.device
+    lut = norm_lut(mean, std, dtype).to(dev)
+    if not 1 <= size <= CROP_MAX_SIZE:
+        raise ValueError(f"size: expected 1..{CROP_MAX_SIZE}, got {size}")
+    crops = torch.empty((end - begin, len(cams), 3, size, size), dtype=dtype, device=dev)
+    geom = torch.empty((end - begin, len(cams), 8), dtype=torch.int32, device=dev)
+    torch.ops.mvmatch_views.crop_views_out(images, scene.contiguous(), views.contiguous(), boxes.contiguous(),
+                                           n_cams, int(scene_base), begin, end - begin, cams, size, fill, lut,
+                                           crops, geom)
+    return crops, geom

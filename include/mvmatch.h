@@ -52,6 +52,8 @@ extern "C" {
                                to ABI 8 (no existing signature or struct changed) */
 #define MVM_HAS_REFINE 1 /* mvm_refine_points: an addition to ABI 8 (no existing signature or
                             struct changed) */
+#define MVM_HAS_CROPS 1 /* mvm_crop_views: an addition to ABI 8 (no existing signature or struct
+                           changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -857,6 +859,54 @@ int mvm_refine_points(const int64_t *match_offs_dev, const int32_t *count_dev, i
                       const double *proj_dev, const int32_t *views_dev, const double *X_dev,
                       int32_t max_evals, double *X_out_dev, double *rms_dev, int32_t *info_dev,
                       double *cov_dev, mvm_stream_t stream);
+
+/*
+ * The pose head's input crops of every match view (an addition to ABI 8,
+ * announced by MVM_HAS_CROPS).  Inputs, none written:
+ *   images_dev uint8 [n_scenes * n_cams, img_h, img_w, 3], contiguous, channel
+ *              order B, G, R; image (s, c) at index s * n_cams + c;
+ *   scene_dev  int32 [>= row0 + n_rows], views_dev int32 [.., n_cams] and
+ *              boxes_dev int32 [.., n_cams, 4] (x1, y1, x2, y2): a match
+ *              table's scene, views (a three-camera table passes its match
+ *              array) and boxes;
+ *   cams_host  n_sel cameras < n_cams on the host, copied into the kernel's
+ *              arguments (never dereferenced on the device);
+ *   lut_dev    float32 [3, 256] (out_kind 0) or float16 [3, 256] (out_kind 1):
+ *              plane c's value of level v, planes in R, G, B order.
+ * A slot is (row r of the n_rows rows from row0, k-th selected camera c).  Its
+ * box is clipped to the image: xa = min(max(x1, 0), img_w), xb, ya, yb alike,
+ * w = xb - xa, h = yb - ya.  With scale = double(size) / max(h, w):
+ * new_w = max(1, rint(w * scale)), new_h alike (fp64, ties to even).  The w x h
+ * crop is resampled to new_w x new_h by the exact box integral: destination
+ * pixel (X, Y) weighs source pixel (i, j) by ox * oy, ox the integer overlap
+ * of [X w, (X + 1) w) with [i new_w, (i + 1) new_w), oy alike; the level is
+ * (2 s + w h) / (2 w h) rounded down, s the weighted sum, in integers (32-bit
+ * while 2 * 255 * w * h < 2^32, else 64-bit: the same value).  The result sits
+ * at ((size - new_h) / 2, (size - new_w) / 2) of a size x size canvas of
+ * `fill`, and out[c][y][x] = lut[c][canvas[y][x][2 - c]].  tests/crop_model.py
+ * states every step; the kernel returns its bits.  Outputs per slot:
+ *   out_dev  [n_rows, n_sel, 3, size, size] of the table's element type;
+ *   geom_dev int32 [n_rows, n_sel, 8], may be NULL: (status, xa, ya, w, h,
+ *            new_w, new_h, image index).  Status 0: crop made; 1: made from a
+ *            clipped box; 2: empty after clipping; 3: no view (views < 0); 4:
+ *            scene - scene_base is no index < n_scenes (checked first).  For 2,
+ *            3 and 4 the canvas is all fill, the fields after the status are 0
+ *            (the image index -1 for status 4) and no image byte is read; no
+ *            entry of views is used as an index.
+ * Every slot of the range is written whole, nothing else.  One launch on
+ * `stream`; no allocation, copy or synchronisation.  n_rows == 0 is MVM_OK
+ * whatever the other arguments are.  Refused before the launch: a NULL pointer
+ * other than geom_dev; n_cams outside 3..MVM_MAX_CAMS; n_sel outside 1..n_cams
+ * or a camera >= n_cams; size outside 1..1024; img_h or img_w outside 1..16384;
+ * fill outside 0..255; out_kind other than 0 or 1; a negative row0, n_rows or
+ * n_scenes; more slots than one launch holds (split the rows).
+ */
+int mvm_crop_views(const uint8_t *images_dev, int32_t n_scenes, int32_t n_cams, int32_t img_h,
+                   int32_t img_w, const int32_t *scene_dev, int32_t scene_base,
+                   const int32_t *views_dev, const int32_t *boxes_dev, int64_t row0, int64_t n_rows,
+                   const int32_t *cams_host, int32_t n_sel, int32_t size, int32_t fill,
+                   const void *lut_dev, int32_t out_kind, void *out_dev, int32_t *geom_dev,
+                   mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

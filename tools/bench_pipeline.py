@@ -17,6 +17,12 @@ every extra pass ("pass 1: ...") and the matches each pass adds are in the line.
 --refine [N] (with --cams C > 3): match_captures(refine=True or N) (DESIGN
 §3.17); the stage "refine" and the distribution of the refinement's status and
 evaluations over the matches are in the line.
+--crops [ROWS] (with --cams C > 3): the pose head's input crops of the batch's
+table (MatchTable.crops) in ranges of ROWS rows (default 256),
+on synthetic uint8 images of --image-size H W held for --image-captures K
+captures (row r reads the images of capture scene[r] mod K: 1000 captures of
+2400 x 2400 images would be 69 GB); the stage time, crops per second and
+output GB/s are in the line, beside the write probe over one range's bytes.
 """
 import argparse
 import json
@@ -71,6 +77,56 @@ def wide_batch(captures, dets, C, seed=5):
     np.cumsum(counts, out=offs[1:])
     boxes = np.concatenate(boxes)
     return boxes, np.full(len(boxes), 0.9, np.float32), np.zeros(len(boxes), np.float32), offs, Ks, RTs
+
+
+def bench_crops(res, args, dev):
+    """--crops: every row of the batch's table through MatchTable.crops in
+    ranges of args.crops rows -> the line's "crops" entry."""
+    import dataclasses
+    from bpc_baseline_amd import ops
+    C, (H, W) = args.cams, args.image_size
+    K = max(1, min(args.image_captures, args.captures))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(318)
+    images = torch.randint(0, 256, (K, C, H, W, 3), dtype=torch.uint8, device=dev, generator=gen)
+    tab = res.table_all() if res.passes else res.table(reproj=True)
+    tab = dataclasses.replace(tab, scene=tab.scene % K)
+    n, step = int(tab.offs[-1]), args.crops
+    dtype = torch.float16 if args.crop_dtype == "float16" else torch.float32
+    ranges = [(b, min(b + step, n)) for b in range(0, n, step)]
+    kw = dict(cams=args.crop_cams, size=args.crop_size, dtype=dtype)
+    for r in ranges[:3]:
+        crops, geom = tab.crops(images, rows=r, **kw)
+    torch.cuda.synchronize()
+    status = np.zeros(5, np.int64)
+    times = []
+    for _ in range(args.steps):
+        t0 = time.perf_counter()
+        for r in ranges:
+            crops, geom = tab.crops(images, rows=r, **kw)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    for r in ranges:
+        status += np.bincount(tab.crops(images, rows=r, **kw)[1][..., 0].reshape(-1).cpu().numpy(), minlength=5)
+    n_sel = C if args.crop_cams is None else len(args.crop_cams)
+    dt = float(np.median(times))
+    out_bytes = n * n_sel * 3 * args.crop_size ** 2 * (2 if dtype == torch.float16 else 4)
+    # the write probe over one range's output bytes, as often as there are ranges
+    buf = torch.empty(min(step, n) * n_sel * 3 * args.crop_size ** 2, dtype=dtype, device=dev)
+    ops.hbm_write_probe(buf)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps * len(ranges)):
+        ops.hbm_write_probe(buf)
+    torch.cuda.synchronize()
+    probe = buf.numel() * buf.element_size() * args.steps * len(ranges) / (time.perf_counter() - t0)
+    return {"rows": n, "rows_per_range": step, "ranges": len(ranges), "cams": n_sel, "size": args.crop_size,
+            "dtype": args.crop_dtype, "image_size": [H, W], "image_captures": K,
+            "stage_ms": dt * 1e3, "stage_ms_all_steps": [round(t * 1e3, 3) for t in times],
+            "crops_per_s": n * n_sel / dt, "output_GBps": out_bytes / dt / 1e9,
+            "write_probe_GBps": probe / 1e9, "status_counts": status.tolist(),
+            "note": "host clock around every range's launch and one device synchronise; the allocation of "
+                    "each range's output (torch's caching allocator) is inside the stage"}
 
 
 def main_wide(args):
@@ -135,6 +191,8 @@ def main_wide(args):
         keep = np.concatenate([np.arange(o, o + n) for o, n in zip(res.offs[:-1], res.count)]
                               + [np.zeros(0, np.int64)]).astype(np.int64)
         out["matches_with_an_extra_view"] = int((v[keep, 3:] >= 0).any(axis=1).sum())
+    if args.crops is not None:
+        out["crops"] = bench_crops(res, args, dev)
     print(json.dumps(out))
 
 
@@ -151,6 +209,16 @@ def main():
                     help="with --cams C > 3: match_captures(extra_seeds=[(a, b, c), ...]) (DESIGN §3.16)")
     ap.add_argument("--refine", type=int, nargs="?", const=0, default=None, metavar="N",
                     help="with --cams C > 3: match_captures(refine=True), or refine=N evaluations (DESIGN §3.17)")
+    ap.add_argument("--crops", type=int, nargs="?", const=256, default=None, metavar="ROWS",
+                    help="with --cams C > 3: MatchTable.crops over the table in ranges of ROWS rows (DESIGN §3.18)")
+    ap.add_argument("--image-size", type=int, nargs=2, default=(2400, 2400), metavar=("H", "W"),
+                    help="with --crops: the synthetic images' size")
+    ap.add_argument("--image-captures", type=int, default=16, metavar="K",
+                    help="with --crops: captures whose images are held (row r reads capture scene[r] mod K)")
+    ap.add_argument("--crop-size", type=int, default=256, help="with --crops: the canvas side")
+    ap.add_argument("--crop-cams", type=lambda v: tuple(int(c) for c in v.split(",")), default=None,
+                    metavar="a[,b...]", help="with --crops: the cameras wanted (default all)")
+    ap.add_argument("--crop-dtype", choices=("float32", "float16"), default="float32")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -168,6 +236,8 @@ def main():
         ap.error("--reproj-gate needs --cams C > 3 without --first-three (it acts on the extra views)")
     if args.refine is not None and (args.cams == 3 or args.first_three):
         ap.error("--refine needs --cams C > 3 without --first-three")
+    if args.crops is not None and (args.cams == 3 or args.first_three or args.crops < 1):
+        ap.error("--crops needs --cams C > 3 without --first-three, and ROWS >= 1")
     if args.cams > 3:
         return main_wide(args)
     dev = torch.device("cuda", 0)
