@@ -212,6 +212,13 @@ SIGNATURES = {
         _i64, _i64, _vp, _i32,              # row0, n_rows, cams (host), n_sel
         _i32, _i32, _vp, _i32,              # size, fill, lut, out_kind
         _vp, _vp, _vp]),                    # out, geom (may be NULL) (out), stream
+    "mvm_fuse_rotations": (ctypes.c_int, [
+        _vp, _i32, _vp, _i32,               # raw, D, scene, scene_base
+        _vp, _vp, _vp, _i32, _i32,          # views, X, RTs, n_scenes, n_cams
+        _i64, _i64, _vp, _i32,              # row0, n_rows, cams (host), n_sel
+        _i32, _i32, _i32,                   # mode, fuse, fuse_cam
+        _vp, _vp, _vp, _vp, _vp, _vp,       # rot_views (may be NULL), R, pose, spread (may be NULL), slot_status, row_status (out)
+        _vp]),                              # stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

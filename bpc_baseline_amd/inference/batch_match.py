@@ -398,6 +398,22 @@ class MatchTable:
         return ops_views.crop_views(images, self.scene, views, self.boxes, self.n_cams, rows=rows, cams=cams,
                                     **kw)
 
+    def poses(self, raw: torch.Tensor, RTs, mode: str, rows=None, cams=None, **kw):
+        """The poses of the table's rows from a rotation head's raw outputs
+        (``ops_views.fuse_rotations`` on the table's own ``scene`` / ``views``
+        / ``X``): ``raw`` float32 [rows, cams, D] on the device,
+        what the head made of ``crops(images, rows=rows, cams=cams)``; ``RTs``
+        f64 [S, n_cams, 4, 4] (host or device); ``mode`` "euler", "quat" or
+        "6d"; ``rows`` and ``cams`` exactly as in ``crops``; the other keywords
+        ``fuse_rotations``'s (``fuse``, ``cam``, ``scene_base``).  Works on the
+        plain three-camera table, on the view table and on ``table_all()``.
+        -> ``ops_views.FusedRotations``: ``pose`` f64 [rows, 4, 4] holds the
+        fused rotation and the row's X (refined where the batch was), ``spread``
+        each view's distance to it."""
+        views = self.views if self.views is not None else self.match
+        return ops_views.fuse_rotations(raw, self.scene, views, self.X, RTs, self.n_cams, mode, rows=rows,
+                                        cams=cams, **kw)
+
 
 def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    img_offs: torch.Tensor, Ks: np.ndarray, RTs: np.ndarray, *,

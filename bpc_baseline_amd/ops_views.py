@@ -13,11 +13,13 @@ fake that returns None.
   mvmatch_views::leftover_gather_out   mvm_leftover_gather
   mvmatch_views::refine_points_out     mvm_refine_points           (DESIGN §3.17)
   mvmatch_views::crop_views_out        mvm_crop_views              (DESIGN §3.18)
+  mvmatch_views::fuse_rotations_out    mvm_fuse_rotations          (DESIGN §3.19)
 """
 from __future__ import annotations
 
 import ctypes
 import math
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -28,11 +30,15 @@ from . import _native, ops
 from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64, u8
 
 __all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points",
-           "norm_lut", "crop_views"]
+           "norm_lut", "crop_views", "fuse_rotations", "FusedRotations"]
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # RGB
 CROP_MAX_SIZE, CROP_MAX_IMAGE = 1024, 16384
 _CROP_KINDS = {torch.float32: 0, torch.float16: 1}
+ROTATION_MODES = {"euler": (0, 3), "quat": (1, 4), "6d": (2, 6)}     # name -> (code, values per slot)
+ROTATION_FUSE = {"cam": 0, "mean": 1}
+SLOT_NO_VIEW, SLOT_NO_CAPTURE, SLOT_DEGENERATE = 1, 2, 4              # FusedRotations.slot_status
+ROW_NO_ROTATION, ROW_AMBIGUOUS = 1, 2                                 # FusedRotations.row_status
 
 
 def _check_gate(gate) -> float:
@@ -238,6 +244,53 @@ def crop_views_out(images: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, 
               ops._p(lut), _CROP_KINDS[out.dtype], ops._p(out), ops._p(geom), ops._stream(images))
 
 
+@ops._gpu_op("fuse_rotations_out", ("rot_views", "R", "pose", "spread", "slot_status", "row_status"),
+             namespace="mvmatch_views")
+def fuse_rotations_out(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs: Tensor, n_cams: int,
+                       scene_base: int, row0: int, n_rows: int, cams: List[int], mode: str, fuse: str,
+                       fuse_cam: int, rot_views: Optional[Tensor], R: Tensor, pose: Tensor,
+                       spread: Optional[Tensor], slot_status: Tensor, row_status: Tensor) -> None:
+    """The rotation head's raw outputs of rows ``row0 : row0 + n_rows`` in the
+    cameras ``cams``, decoded, taken to the world and fused into a pose per row
+    (mvm_fuse_rotations).  ``raw`` / ``scene`` / ``views`` / ``X`` / ``RTs`` are
+    read only; ``rot_views`` / ``spread`` (None: not written) and the others out."""
+    dev = ops._gpu(raw, "raw", "rotation kernel")
+    if not 3 <= n_cams <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if mode not in ROTATION_MODES:
+        raise ValueError(f"mode: expected one of {sorted(ROTATION_MODES)}, got {mode!r}")
+    if fuse not in ROTATION_FUSE:
+        raise ValueError(f"fuse: expected one of {sorted(ROTATION_FUSE)}, got {fuse!r}")
+    if not 1 <= len(cams) <= n_cams or not all(0 <= c < n_cams for c in cams):
+        raise ValueError(f"cams: expected 1..{n_cams} cameras < {n_cams}, got {list(cams)}")
+    if fuse == "cam" and fuse_cam not in cams:
+        raise ValueError(f"cam: camera {fuse_cam} is not among the selected cameras {list(cams)}")
+    if row0 < 0 or n_rows < 0:
+        raise ValueError(f"rows: expected 0 <= begin <= end, got ({row0}, {row0 + n_rows})")
+    if RTs.dim() != 4 or tuple(RTs.shape[1:]) != (n_cams, 4, 4):
+        raise ValueError(f"RTs must be [S, {n_cams}, 4, 4], got {tuple(RTs.shape)}")
+    (code, D), S = ROTATION_MODES[mode], int(RTs.shape[0])
+    n_end, n_slots = row0 + n_rows, n_rows * len(cams)
+    rows = [(raw, "raw", f32, D * n_slots, EXACT), (scene, "scene", i32, n_end, AT_LEAST),
+            (views, "views", i32, n_cams * n_end, AT_LEAST), (X, "X", f64, 3 * n_end, AT_LEAST),
+            (RTs, "RTs", f64, 16 * n_cams * S, EXACT), (R, "R", f64, 9 * n_rows, EXACT),
+            (pose, "pose", f64, 16 * n_rows, EXACT), (slot_status, "slot_status", i32, n_slots, EXACT),
+            (row_status, "row_status", i32, n_rows, EXACT)]
+    if rot_views is not None:
+        rows.append((rot_views, "rot_views", f64, 9 * n_slots, EXACT))
+    if spread is not None:
+        rows.append((spread, "spread", f64, n_slots, EXACT))
+    ops._check_args(dev, rows)
+    if n_rows == 0:
+        return                       # no row: nothing to launch
+    if S == 0:
+        raise ValueError("RTs holds no capture")
+    ops._call("mvm_fuse_rotations", ops._p(raw), D, ops._p(scene), scene_base, ops._p(views), ops._p(X),
+              ops._p(RTs), S, n_cams, row0, n_rows, (ctypes.c_int32 * len(cams))(*cams), len(cams), code,
+              ROTATION_FUSE[fuse], fuse_cam, ops._p(rot_views), ops._p(R), ops._p(pose), ops._p(spread),
+              ops._p(slot_status), ops._p(row_status), ops._stream(raw))
+
+
 def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
               seed=(0, 1, 2), sub_cam_offs: Optional[Tensor] = None, orig: Optional[Tensor] = None) -> Tensor:
     """Flag the detections the matches of one pass hold (device).
@@ -399,3 +452,71 @@ def crop_views(images: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, n_ca
                                            n_cams, int(scene_base), begin, end - begin, cams, size, fill, lut,
                                            crops, geom)
     return crops, geom
+
+
+@dataclass
+class FusedRotations:
+    """What ``fuse_rotations`` returns, on the device (n rows, K selected cameras)."""
+    R: Tensor                    # float64 [n, 3, 3]     the row's rotation (object -> world), NaN without one
+    pose: Tensor                 # float64 [n, 4, 4]     [[R, X], [0, 0, 0, 1]]
+    rot_views: Tensor            # float64 [n, K, 3, 3]  each view's rotation in the world, NaN where unusable
+    spread: Tensor               # float64 [n, K]        |rot_views - R|_F^2: 0 .. 8, NaN where either is NaN
+    slot_status: Tensor          # int32 [n, K]          0, SLOT_NO_VIEW, SLOT_NO_CAPTURE or SLOT_DEGENERATE
+    row_status: Tensor           # int32 [n]             0, ROW_NO_ROTATION or ROW_AMBIGUOUS
+
+
+def fuse_rotations(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs, n_cams: int, mode: str,
+                   rows: Optional[Sequence[int]] = None, cams: Optional[Sequence[int]] = None,
+                   fuse: str = "cam", cam: int = 2, scene_base: int = 0) -> FusedRotations:
+    """From a rotation head's raw outputs to a pose per match (device; DESIGN
+    §3.19).  ``raw`` float32 [rows, cams, D]: the head's output for the crops
+    ``crop_views`` made with the same ``rows`` and ``cams``; ``mode`` "euler"
+    (D = 3, radians), "quat" (D = 4: x, y, z, w) or "6d" (D = 6).  ``scene``
+    int32 [n], ``views`` int32 [n, n_cams] (a three-camera table: its
+    ``match``) and ``X`` f64 [n, 3] a ``MatchTable``'s fields, none written;
+    ``RTs`` f64 [S, n_cams, 4, 4] (world -> camera), a host array (copied once)
+    or a device tensor.  Per slot the raw vector is decoded in float32 as the
+    reference decodes it and taken to the world, ``RTs[s, c, :3, :3].T @ M``
+    in float64.  Per row the usable slots are fused: ``fuse="cam"`` keeps
+    camera ``cam``'s rotation (default 2, the reference's ``final_rotation``),
+    ``fuse="mean"`` takes the chordal mean of them all.  tests/pose_model.py
+    states every step; the result is its bits.
+    -> ``FusedRotations``.  ``slot_status``: SLOT_NO_CAPTURE where ``scene -
+    scene_base`` is no capture of ``RTs``, SLOT_NO_VIEW where ``views < 0``,
+    SLOT_DEGENERATE where the decoded matrix is not finite (a zero quaternion,
+    a NaN).  ``row_status``: ROW_NO_ROTATION where no usable slot was left (R
+    NaN), ROW_AMBIGUOUS where the mean is not determined (views half a turn
+    apart; R still written).  ``spread`` is the caller's consistency gate."""
+    n_cams = int(n_cams)
+    n = int(scene.shape[0])
+    if rows is None:
+        rows = (0, n)
+    try:
+        begin, end = (int(r) for r in rows)
+    except (TypeError, ValueError):
+        raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+    if not 0 <= begin <= end <= n:
+        raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+    cams = list(range(n_cams)) if cams is None else [int(c) for c in cams]
+    if mode not in ROTATION_MODES:
+        raise ValueError(f"mode: expected one of {sorted(ROTATION_MODES)}, got {mode!r}")
+    if fuse not in ROTATION_FUSE:
+        raise ValueError(f"fuse: expected one of {sorted(ROTATION_FUSE)}, got {fuse!r}")
+    if isinstance(cam, bool) or not isinstance(cam, int):
+        raise ValueError(f"cam: expected a camera, got {cam!r}")
+    if fuse == "cam" and cam not in cams:
+        raise ValueError(f"cam: camera {cam} is not among the selected cameras {cams}")
+    dev = raw.device
+    m, K, D = end - begin, len(cams), ROTATION_MODES[mode][1]
+    if raw.dim() != 3 or tuple(raw.shape) != (m, K, D):
+        raise ValueError(f"raw must be [{m}, {K}, {D}] for mode {mode!r}, got {tuple(raw.shape)}")
+    if not isinstance(RTs, Tensor):
+        RTs = torch.from_numpy(np.ascontiguousarray(RTs, np.float64)).to(dev)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = FusedRotations(R=e((m, 3, 3), f64), pose=e((m, 4, 4), f64), rot_views=e((m, K, 3, 3), f64),
+                         spread=e((m, K), f64), slot_status=e((m, K), i32), row_status=e(m, i32))
+    torch.ops.mvmatch_views.fuse_rotations_out(raw, scene.contiguous(), views.contiguous(), X.contiguous(),
+                                               RTs.contiguous(), n_cams, int(scene_base), begin, m, cams, mode,
+                                               fuse, cam, out.rot_views, out.R, out.pose, out.spread,
+                                               out.slot_status, out.row_status)
+    return out

@@ -54,6 +54,8 @@ extern "C" {
                             struct changed) */
 #define MVM_HAS_CROPS 1 /* mvm_crop_views: an addition to ABI 8 (no existing signature or struct
                            changed) */
+#define MVM_HAS_POSES 1 /* mvm_fuse_rotations: an addition to ABI 8 (no existing signature or
+                           struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -907,6 +909,62 @@ int mvm_crop_views(const uint8_t *images_dev, int32_t n_scenes, int32_t n_cams, 
                    const int32_t *cams_host, int32_t n_sel, int32_t size, int32_t fill,
                    const void *lut_dev, int32_t out_kind, void *out_dev, int32_t *geom_dev,
                    mvm_stream_t stream);
+
+/*
+ * From the rotation head's raw outputs to a pose per match (an addition to
+ * ABI 8, announced by MVM_HAS_POSES).  Inputs, none
+ * written:
+ *   raw_dev    float32 [n_rows, n_sel, D]: the head's output per slot; D = 3
+ *              (mode 0, Euler angles in radians), 4 (mode 1, quaternion x, y,
+ *              z, w) or 6 (mode 2, the 6-D representation);
+ *   scene_dev  int32 [>= row0 + n_rows], views_dev int32 [.., n_cams] and X_dev
+ *              f64 [.., 3]: a match table's scene, views (a three-camera table
+ *              passes its match array) and X;
+ *   RTs_dev    f64 [n_scenes, n_cams, 4, 4]: world -> camera;
+ *   cams_host  n_sel cameras < n_cams on the host, copied into the kernel's
+ *              arguments (never dereferenced on the device).
+ * A slot is (row r of the n_rows rows from row0, k-th selected camera c).  Its
+ * raw vector is decoded in float32 as the reference decodes it: mode 0 wraps
+ * each angle to ((a + pi) mod 2 pi) - pi, takes the float64 sine and cosine
+ * rounded once and forms rotmat_from_euler's entries; mode 1 divides by
+ * (norm + 1e-8), then by the norm, and forms quat_to_rotmat's entries; mode 2
+ * is rotmat_from_6d's Gram-Schmidt step with norms clamped at 1e-8.  The
+ * float32 matrix M goes to the world in float64: W = RTs[s][c][:3][:3]^T M.
+ * Slot status: 2 where scene - scene_base is no index < n_scenes (checked
+ * first), 1 where views < 0, 4 where M has a non-finite entry, else 0.  A row
+ * is fused over its slots of status 0, in the order of cams_host:
+ *   fuse 0  the rotation of camera fuse_cam, which must be selected; row
+ *           status 1 where that slot's status is not 0;
+ *   fuse 1  the chordal mean: the rotation nearest the sum of the W, as the
+ *           largest eigenvector of Horn's symmetric 4 x 4 matrix (8 sweeps of
+ *           cyclic Jacobi rotations and one shifted power step, float64); row
+ *           status 1 where no slot is usable, 2 where the two largest
+ *           eigenvalues differ by no more than 1e-9 times the usable slots (for
+ *           example two views half a turn apart; R is still written).
+ * tests/pose_model.py states every step; the kernel returns its bits.  Outputs
+ * per row or slot of the range:
+ *   rot_views_dev   f64 [n_rows, n_sel, 3, 3], may be NULL: W, NaN where the
+ *                   slot's status is not 0;
+ *   R_dev           f64 [n_rows, 3, 3]: the fused rotation, NaN for row status 1;
+ *   pose_dev        f64 [n_rows, 4, 4]: [[R, X], [0, 0, 0, 1]];
+ *   spread_dev      f64 [n_rows, n_sel], may be NULL: the squared Frobenius
+ *                   distance of W to R (0 .. 8), NaN where either is NaN;
+ *   slot_status_dev int32 [n_rows, n_sel]; row_status_dev int32 [n_rows].
+ * No entry of views is used as an index.  One launch on `stream`, a thread per
+ * row; no allocation, copy or synchronisation.  n_rows == 0 is MVM_OK whatever
+ * the other arguments are.  Refused before the launch: a NULL pointer other
+ * than rot_views_dev and spread_dev; n_cams outside 3..MVM_MAX_CAMS; n_sel
+ * outside 1..n_cams or a camera >= n_cams; a mode or fuse not listed; D that
+ * is not the mode's; fuse 0 with fuse_cam not selected; a negative row0,
+ * n_rows or n_scenes.
+ */
+int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev, int32_t scene_base,
+                       const int32_t *views_dev, const double *X_dev, const double *RTs_dev,
+                       int32_t n_scenes, int32_t n_cams, int64_t row0, int64_t n_rows,
+                       const int32_t *cams_host, int32_t n_sel, int32_t mode, int32_t fuse,
+                       int32_t fuse_cam, double *rot_views_dev, double *R_dev, double *pose_dev,
+                       double *spread_dev, int32_t *slot_status_dev, int32_t *row_status_dev,
+                       mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

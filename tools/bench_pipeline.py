@@ -23,6 +23,12 @@ on synthetic uint8 images of --image-size H W held for --image-captures K
 captures (row r reads the images of capture scene[r] mod K: 1000 captures of
 2400 x 2400 images would be 69 GB); the stage time, crops per second and
 output GB/s are in the line, beside the write probe over one range's bytes.
+--poses MODE (with --cams C > 3; euler, quat, 6d or all): the batch's table
+through MatchTable.poses on random raw vectors, all rows, all
+cameras, fuse="mean"; the stage time (host clock around the launch and one
+synchronise, median of --steps) is in the line, beside the same work done on the
+host one row at a time through tests/pose_model.py, timed on --cpu-sample rows
+and scaled to the table.
 """
 import argparse
 import json
@@ -129,6 +135,48 @@ def bench_crops(res, args, dev):
                     "each range's output (torch's caching allocator) is inside the stage"}
 
 
+def bench_poses(res, args, dev, RTs):
+    """--poses: every row and camera of the batch's table through
+    MatchTable.poses -> the line's "poses" entry, one item per mode."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import pose_model as M
+    C = args.cams
+    tab = res.table_all() if res.passes else res.table(reproj=True)
+    n = int(tab.offs[-1])
+    RTs = np.ascontiguousarray(RTs, np.float64)
+    rts_dev = torch.from_numpy(RTs).to(dev)
+    host = tab.host()
+    rng = np.random.default_rng(319)
+    out = {"rows": n, "cams": C, "fuse": "mean", "modes": {}}
+    for mode in (("euler", "quat", "6d") if args.poses == "all" else (args.poses,)):
+        raw_h = M.random_raw(rng, n * C, mode).reshape(n, C, -1)
+        raw = torch.from_numpy(raw_h).to(dev)
+        for _ in range(3):
+            got = tab.poses(raw, rts_dev, mode, fuse="mean")
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            got = tab.poses(raw, rts_dev, mode, fuse="mean")
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        k = max(1, min(args.cpu_sample, n))
+        t0 = time.perf_counter()
+        for r in range(k):
+            M.fuse_rotations(raw_h[r:r + 1], host["scene"], host["views"], host["X"], RTs, mode, rows=(r, r + 1),
+                             fuse="mean")
+        per_row = (time.perf_counter() - t0) / k
+        out["modes"][mode] = {"stage_ms": float(np.median(times)) * 1e3,
+                              "stage_ms_all_steps": [round(t * 1e3, 4) for t in times],
+                              "slots_per_s": n * C / float(np.median(times)),
+                              "host_row_at_a_time_ms": per_row * n * 1e3, "host_rows_timed": k,
+                              "row_status_counts": np.bincount(got.row_status.cpu().numpy(), minlength=3).tolist()}
+    out["note"] = ("host clock around the launch and one device synchronise; the allocation of the outputs "
+                   "(torch's caching allocator) is inside the stage; the host figure is the numpy model called "
+                   "on one row at a time, scaled from host_rows_timed rows to the table")
+    return out
+
+
 def main_wide(args):
     """--cams C > 3: ms per batch and synchronised stage times of
     match_captures(n_cams=C), or (--first-three) of the three-camera chain on
@@ -193,6 +241,8 @@ def main_wide(args):
         out["matches_with_an_extra_view"] = int((v[keep, 3:] >= 0).any(axis=1).sum())
     if args.crops is not None:
         out["crops"] = bench_crops(res, args, dev)
+    if args.poses is not None:
+        out["poses"] = bench_poses(res, args, dev, RTs)
     print(json.dumps(out))
 
 
@@ -219,6 +269,8 @@ def main():
     ap.add_argument("--crop-cams", type=lambda v: tuple(int(c) for c in v.split(",")), default=None,
                     metavar="a[,b...]", help="with --crops: the cameras wanted (default all)")
     ap.add_argument("--crop-dtype", choices=("float32", "float16"), default="float32")
+    ap.add_argument("--poses", choices=("euler", "quat", "6d", "all"), default=None, metavar="MODE",
+                    help="with --cams C > 3: MatchTable.poses over the table, fuse=\"mean\" (DESIGN §3.19)")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -238,6 +290,8 @@ def main():
         ap.error("--refine needs --cams C > 3 without --first-three")
     if args.crops is not None and (args.cams == 3 or args.first_three or args.crops < 1):
         ap.error("--crops needs --cams C > 3 without --first-three, and ROWS >= 1")
+    if args.poses is not None and (args.cams == 3 or args.first_three):
+        ap.error("--poses needs --cams C > 3 without --first-three")
     if args.cams > 3:
         return main_wide(args)
     dev = torch.device("cuda", 0)
