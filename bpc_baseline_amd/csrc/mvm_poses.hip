@@ -26,6 +26,10 @@ enum : int32_t { kRowNoRotation = 1, kRowAmbiguous = 2 };
 
 constexpr int kJacobiSweeps = 8;
 constexpr double kAmbiguousGap = 1e-9;
+// a world rotation with an entry of 2^500 or more in magnitude is degenerate:
+// below it the sum of eight, Horn's combinations, the power step's squares and
+// the spread's nine stay finite
+constexpr int kWorldMaxExp = 500;
 constexpr float kEps32 = 1e-8f;
 constexpr float kPi32 = (float)3.14159265358979323846;
 constexpr float kTwoPi32 = (float)6.28318530717958647692;
@@ -102,6 +106,11 @@ __device__ __forceinline__ void decode(const float *__restrict__ raw, float m[9]
     }
 }
 
+// |x| < 2^kWorldMaxExp, false for a NaN: the biased exponent alone decides
+__device__ __forceinline__ bool below_world_max(double x) {
+    return (uint32_t)(__double2hiint(x) & 0x7fffffff) < ((uint32_t)(1023 + kWorldMaxExp) << 20);
+}
+
 // What one thread knows of its row
 struct PoseRow {
     const float *raw;        // the row's first raw vector
@@ -110,7 +119,8 @@ struct PoseRow {
     uint32_t cams_packed;
 };
 
-// Slot k of the row -> its status and, where that is 0, W = R_c^T M in float64
+// Slot k of the row -> its status and, where that is 0, W = R_c^T M in float64;
+// degenerate where M has a non-finite entry or W one that is not below_world_max
 template <int MODE>
 __device__ __forceinline__ int32_t slot_world(const PoseRow &row, int k, double W[9]) {
     if (!row.rts) return kSlotNoCapture;
@@ -128,6 +138,12 @@ __device__ __forceinline__ int32_t slot_world(const PoseRow &row, int k, double 
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             W[3 * i + j] = (R[i] * (double)m[j] + R[4 + i] * (double)m[3 + j]) + R[8 + i] * (double)m[6 + j];
+    // a NaN, an infinity or an absurd magnitude from the extrinsic rotation: no
+    // rotation either
+    bool sane = true;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) sane = sane && below_world_max(W[e]);
+    if (!sane) return kSlotDegenerate;
     return 0;
 }
 

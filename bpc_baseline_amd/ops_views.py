@@ -461,7 +461,8 @@ class FusedRotations:
     pose: Tensor                 # float64 [n, 4, 4]     [[R, X], [0, 0, 0, 1]]
     rot_views: Tensor            # float64 [n, K, 3, 3]  each view's rotation in the world, NaN where unusable
     spread: Tensor               # float64 [n, K]        |rot_views - R|_F^2: 0 .. 8, NaN where either is NaN
-    slot_status: Tensor          # int32 [n, K]          0, SLOT_NO_VIEW, SLOT_NO_CAPTURE or SLOT_DEGENERATE
+    slot_status: Tensor          # int32 [n, K]          0, SLOT_NO_VIEW, SLOT_NO_CAPTURE or SLOT_DEGENERATE (the
+    #                                                    decoded matrix not finite, its world product not below 2^500)
     row_status: Tensor           # int32 [n]             0, ROW_NO_ROTATION or ROW_AMBIGUOUS
 
 
@@ -484,9 +485,13 @@ def fuse_rotations(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs, n_
     -> ``FusedRotations``.  ``slot_status``: SLOT_NO_CAPTURE where ``scene -
     scene_base`` is no capture of ``RTs``, SLOT_NO_VIEW where ``views < 0``,
     SLOT_DEGENERATE where the decoded matrix is not finite (a zero quaternion,
-    a NaN).  ``row_status``: ROW_NO_ROTATION where no usable slot was left (R
-    NaN), ROW_AMBIGUOUS where the mean is not determined (views half a turn
-    apart; R still written).  ``spread`` is the caller's consistency gate."""
+    a NaN) or its world product has an entry that is not below 2^500 in
+    magnitude (a NaN, infinite or absurd rotation block of ``RTs``).
+    ``row_status``: ROW_NO_ROTATION where no usable slot
+    was left (R NaN), ROW_AMBIGUOUS where the mean is not determined (views
+    half a turn apart; R still written).  ``R`` is NaN only under
+    ROW_NO_ROTATION and ``rot_views`` only where ``slot_status`` is not 0,
+    whatever ``RTs`` holds.  ``spread`` is the caller's consistency gate."""
     n_cams = int(n_cams)
     n = int(scene.shape[0])
     if rows is None:

@@ -931,7 +931,11 @@ int mvm_crop_views(const uint8_t *images_dev, int32_t n_scenes, int32_t n_cams, 
  * is rotmat_from_6d's Gram-Schmidt step with norms clamped at 1e-8.  The
  * float32 matrix M goes to the world in float64: W = RTs[s][c][:3][:3]^T M.
  * Slot status: 2 where scene - scene_base is no index < n_scenes (checked
- * first), 1 where views < 0, 4 where M has a non-finite entry, else 0.  A row
+ * first), 1 where views < 0, 4 where M has a non-finite entry (a zero
+ * quaternion, a NaN or infinite input) or W an entry that is not below 2^500
+ * in magnitude (a NaN, an infinity or an absurd value in the extrinsic
+ * rotation), else 0.  So R is NaN only for row status 1 and
+ * rot_views only where the slot's status is not 0, whatever RTs holds.  A row
  * is fused over its slots of status 0, in the order of cams_host:
  *   fuse 0  the rotation of camera fuse_cam, which must be selected; row
  *           status 1 where that slot's status is not 0;

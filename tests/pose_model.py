@@ -26,6 +26,9 @@ PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))      # one Jacobi sweep
 SWEEPS = 8
 AMBIGUOUS_GAP = 1e-9                                          # lambda1 - lambda2 <= GAP * n_used
 EULER_MARGIN = 2.0 ** -40                                     # euler_filter
+# a world rotation with a non-finite entry, or one of this magnitude or more, is DEGENERATE: below it the sum of
+# eight, Horn's combinations of three, the power step's four squares and the spread's nine all stay finite
+WORLD_MAX = 2.0 ** 500
 
 F1, F2, EPS32 = np.float32(1), np.float32(2), np.float32(1e-8)
 PI32, TWO_PI32 = np.float32(np.pi), np.float32(2 * np.pi)
@@ -235,6 +238,10 @@ def fuse_rotations(raw, scene, views, X, RTs, mode, rows=None, cams=None, fuse="
         M = decode(raw[:, k], mode)
         st = np.where((st == 0) & ~np.isfinite(M).all(axis=(1, 2)), DEGENERATE, st).astype(np.int32)
         Wk = to_world(RTs[np.where(in_range, sc, 0), c, :3, :3], M) if S else np.full((m, 3, 3), np.nan)
+        # a NaN, an infinity or an absurd magnitude from the extrinsic rotation (a NaN fails the comparison)
+        with np.errstate(invalid="ignore"):
+            sane = (np.abs(Wk) < WORLD_MAX).all(axis=(1, 2))
+        st = np.where((st == 0) & ~sane, DEGENERATE, st).astype(np.int32)
         W[:, k] = np.where((st == 0)[:, None, None], Wk, np.nan)
         status[:, k] = st
     used = status == 0
@@ -263,6 +270,27 @@ def fuse_rotations(raw, scene, views, X, RTs, mode, rows=None, cams=None, fuse="
     pose[:, :3, 3] = np.asarray(X, np.float64)[b:e]
     pose[:, 3, 3] = 1.0
     return dict(rot_views=W, R=R, pose=pose, spread=spread, slot_status=status, row_status=row_status, lam=lam)
+
+
+def invariants(out):
+    """What a result promises whatever its inputs hold, asserted on a dict of
+    ``fuse_rotations``' outputs (the model's or the device's; ``rot_views``
+    and ``spread`` may be absent): R is finite unless the row has
+    NO_ROTATION and NaN where it has; a slot's rot_views are finite if and only
+    if its status is 0; its spread is finite if and only if it is usable and
+    the row has a rotation."""
+    has = (np.asarray(out["row_status"]) & NO_ROTATION) == 0
+    usable = np.asarray(out["slot_status"]) == 0
+    assert np.isin(out["row_status"], (0, NO_ROTATION, AMBIGUOUS)).all()
+    assert np.isin(out["slot_status"], (0, NO_VIEW, NO_CAPTURE, DEGENERATE)).all()
+    assert (np.isfinite(out["R"]).all(axis=(1, 2)) == has).all(), "R finite <=> the row has a rotation"
+    assert np.isnan(out["R"][~has]).all() and (has <= usable.any(axis=1)).all()
+    assert same(np.ascontiguousarray(out["pose"][:, :3, :3]), out["R"])
+    if "rot_views" in out:
+        assert (np.isfinite(out["rot_views"]).all(axis=(2, 3)) == usable).all(), "rot_views finite <=> slot status 0"
+        assert np.isnan(out["rot_views"][~usable]).all()
+    if "spread" in out:
+        assert (np.isfinite(out["spread"]) == (usable & has[:, None])).all(), "spread finite <=> usable and fused"
 
 
 # ---- inputs ---------------------------------------------------------------------------------

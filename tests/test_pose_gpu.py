@@ -120,6 +120,7 @@ def check(c, dev, rows, cams, fuse, cam=2, omit=()):
     got, want = run_op(c, dev, rows, cams, fuse, cam, omit), expected(c, rows, cams, fuse, cam)
     for k, v in got.items():
         assert M.same(v, want[k]), (k, np.argwhere(~((v == want[k]) | ((v != v) & (want[k] != want[k]))))[:5])
+    M.invariants(got)
     return want
 
 
