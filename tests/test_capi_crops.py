@@ -21,9 +21,11 @@ def lib():
     return _native.load()
 
 
-def _call(lib, null=None, every=FAKE, cams=(0, 1), **kw):
+def _call(lib, null=None, every=FAKE, cams=(0, 1), out=None, **kw):
     a = dict(DEFAULTS, **kw)
     p = {name: (None if name == null else every) for name in POINTERS}
+    if out is not None:
+        p["out_dev"] = out
     if p["cams_host"] is not None:
         p["cams_host"] = (ctypes.c_int32 * max(len(cams), 1))(*cams)
     return lib.mvm_crop_views(p["images_dev"], a["n_scenes"], a["n_cams"], a["img_h"], a["img_w"],
@@ -104,3 +106,21 @@ def test_no_rows_launches_nothing(lib):
     assert _call(lib, n_rows=0) == 0
     assert _call(lib, n_rows=0, n_cams=9, size=0, fill=700, img_h=-3, out_kind=5, cams=(11,)) == 0
     assert lib.mvm_last_error_string() == b""
+
+
+KMAX_GRID_BLOCKS = 16777215          # kMaxGridBlocks: what one launch holds
+
+
+@pytest.mark.parametrize("size, out, n_rows, blocks", [
+    (1024, 0x1000, 8192, 256),       # aligned: 4096 pixels a workgroup
+    (1024, 0x1004, 2048, 1024),      # unaligned: 1024 pixels a workgroup
+    (1023, 0x1000, 2051, 1023),      # an odd side writes elements wherever it starts
+])
+def test_more_crops_than_one_launch_holds(lib, size, out, n_rows, blocks):
+    """Each is the first row count refused: nothing is launched, so the fake
+    pointers are never read.  (The accepted side would launch: not called.)"""
+    assert blocks == -(-size * size // (4096 if size % 2 == 0 and out % 16 == 0 else 1024))
+    assert n_rows * 8 * blocks > KMAX_GRID_BLOCKS >= (n_rows - 1) * 8 * blocks
+    assert _call(lib, cams=tuple(range(8)), n_cams=8, size=size, n_rows=n_rows, out=ctypes.c_void_p(out)) == 2
+    msg = lib.mvm_last_error_string()                     # MVM_ERR_UNSUPPORTED
+    assert b"n_rows=%d" % n_rows in msg and b"split the rows" in msg
