@@ -219,6 +219,17 @@ SIGNATURES = {
         _i32, _i32, _i32,                   # mode, fuse, fuse_cam
         _vp, _vp, _vp, _vp, _vp, _vp,       # rot_views (may be NULL), R, pose, spread (may be NULL), slot_status, row_status (out)
         _vp]),                              # stream
+    "mvm_score_poses": (ctypes.c_int, [
+        _vp, _vp, _i32,                     # pose, scene, scene_base
+        _vp, _vp, _i32, _i32,               # gt_pose, gt_offs, n_scenes, g_max
+        _vp, _i32, _vp, _i32,               # verts, n_verts, syms, n_syms
+        _i64, _i64,                         # row0, n_rows
+        _vp, _vp, _vp, _vp,                 # err, sym, t_err (may be NULL), rot_cos (may be NULL) (out)
+        _vp]),                              # stream
+    "mvm_match_scores": (ctypes.c_int, [
+        _vp, _i32, _vp, _vp, _i32,          # err, g_max, row_offs, gt_offs, n_scenes
+        _vp, _i32,                          # thresholds (host), n_thresholds
+        _vp, _vp, _i64, _vp]),              # gt_index, tp (out), n_rows_total, stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -414,6 +414,50 @@ class MatchTable:
         return ops_views.fuse_rotations(raw, self.scene, views, self.X, RTs, self.n_cams, mode, rows=rows,
                                         cams=cams, **kw)
 
+    def score(self, gt_pose, gt_offs, verts=None, syms=None, pose=None, thresholds=None, rows=None,
+              scene_base: int = 0):
+        """The table's rows against ground truth (``ops_views.score_poses`` on
+        the table's own ``scene``): ``gt_pose`` f64 [G, 4, 4] the
+        ground-truth poses in the world frame, ``gt_offs`` int64 [S + 1] each
+        capture's rows among them (host or device).  With ``pose=None`` the
+        estimates are identity rotations with the table's ``X`` and ``verts``
+        defaults to the single origin: ``err`` is then the distance of the
+        centres, which scores the matcher alone, with no head.  With
+        ``pose=fused.pose`` (f64 [rows, 4, 4]) and ``rows`` as given to
+        ``poses`` it scores full poses over ``verts`` f64 [V, 3] and ``syms``
+        f64 [K, 4, 4] (default the identity).  ``thresholds`` (1..16 numbers):
+        the rows are also matched greedily to the ground truth per capture
+        (``ops_views.match_scores`` with the table's ``offs``); matching is per
+        whole capture, so it needs ``rows=None``.  Works on the plain
+        three-camera table, on the view table and on ``table_all()``.
+        -> ``ops_views.PoseScores``, with ``gt_index`` / ``tp`` set where
+        ``thresholds`` is given (``ops_views.recall_precision`` takes ``tp``)."""
+        n = int(self.scene.shape[0])
+        if thresholds is not None and rows is not None:
+            raise ValueError("thresholds: matching is per whole capture and needs rows=None")
+        if rows is None:
+            rows = (0, n)
+        try:
+            begin, end = (int(r) for r in rows)
+        except (TypeError, ValueError):
+            raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+        if not 0 <= begin <= end <= n:
+            raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+        if pose is None:
+            pose = torch.eye(4, dtype=torch.float64, device=self.X.device).repeat(end - begin, 1, 1)
+            pose[:, :3, 3] = self.X[begin:end]
+            if verts is None:
+                verts = np.zeros((1, 3))
+        elif verts is None:
+            raise ValueError("verts: a full pose is scored over the model's vertices")
+        if pose.dim() != 3 or tuple(pose.shape) != (end - begin, 4, 4):
+            raise ValueError(f"pose must be [{end - begin}, 4, 4], got {tuple(pose.shape)}")
+        res = ops_views.score_poses(pose, self.scene[begin:end], gt_pose, gt_offs, verts, syms,
+                                    scene_base=scene_base)
+        if thresholds is not None:
+            res.gt_index, res.tp = ops_views.match_scores(res.err, self.offs, gt_offs, thresholds)
+        return res
+
 
 def match_captures(boxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor,
                    img_offs: torch.Tensor, Ks: np.ndarray, RTs: np.ndarray, *,

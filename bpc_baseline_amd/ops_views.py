@@ -14,6 +14,8 @@ fake that returns None.
   mvmatch_views::refine_points_out     mvm_refine_points           (DESIGN §3.17)
   mvmatch_views::crop_views_out        mvm_crop_views              (DESIGN §3.18)
   mvmatch_views::fuse_rotations_out    mvm_fuse_rotations          (DESIGN §3.19)
+  mvmatch_views::score_poses_out       mvm_score_poses             (DESIGN §3.20)
+  mvmatch_views::match_scores_out      mvm_match_scores
 """
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ from . import _native, ops
 from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64, u8
 
 __all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points",
-           "norm_lut", "crop_views", "fuse_rotations", "FusedRotations"]
+           "norm_lut", "crop_views", "fuse_rotations", "FusedRotations", "score_poses", "match_scores",
+           "recall_precision", "PoseScores"]
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # RGB
 CROP_MAX_SIZE, CROP_MAX_IMAGE = 1024, 16384
@@ -39,6 +42,9 @@ ROTATION_MODES = {"euler": (0, 3), "quat": (1, 4), "6d": (2, 6)}     # name -> (
 ROTATION_FUSE = {"cam": 0, "mean": 1}
 SLOT_NO_VIEW, SLOT_NO_CAPTURE, SLOT_DEGENERATE = 1, 2, 4              # FusedRotations.slot_status
 ROW_NO_ROTATION, ROW_AMBIGUOUS = 1, 2                                 # FusedRotations.row_status
+SYM_PADDING, SYM_NO_CAPTURE, SYM_NOT_FINITE = -1, -2, -3              # PoseScores.sym below 0
+SCORE_MAX_SYMS, SCORE_MAX_THRESHOLDS, SCORE_MAX_MATCH_GT = 64, 16, 1024
+SCORE_POSE_MAX = 2.0 ** 200
 
 
 def _check_gate(gate) -> float:
@@ -291,6 +297,76 @@ def fuse_rotations_out(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs
               ops._p(slot_status), ops._p(row_status), ops._stream(raw))
 
 
+@ops._gpu_op("score_poses_out", ("err", "sym", "t_err", "rot_cos"), namespace="mvmatch_views")
+def score_poses_out(pose: Tensor, scene: Tensor, gt_pose: Tensor, gt_offs: Tensor, verts: Tensor, syms: Tensor,
+                    scene_base: int, g_max: int, row0: int, n_rows: int, err: Tensor, sym: Tensor,
+                    t_err: Optional[Tensor], rot_cos: Optional[Tensor]) -> None:
+    """The pose error of rows ``row0 : row0 + n_rows`` against every
+    ground-truth object of their capture (mvm_score_poses).  ``pose`` /
+    ``scene`` / ``gt_pose`` / ``gt_offs`` / ``verts`` / ``syms`` are read only
+    (``gt_offs`` is trusted: non-decreasing and within ``gt_pose``); ``err`` /
+    ``sym`` and ``t_err`` / ``rot_cos`` (None: not written) out."""
+    dev = ops._gpu(pose, "pose", "pose scorer")
+    if row0 < 0 or n_rows < 0:
+        raise ValueError(f"rows: expected 0 <= begin <= end, got ({row0}, {row0 + n_rows})")
+    if g_max < 1:
+        raise ValueError(f"g_max: expected at least 1, got {g_max}")
+    if pose.dim() != 3 or tuple(pose.shape[1:]) != (4, 4):
+        raise ValueError(f"pose must be [n, 4, 4], got {tuple(pose.shape)}")
+    if gt_pose.dim() != 3 or tuple(gt_pose.shape[1:]) != (4, 4):
+        raise ValueError(f"gt_pose must be [G, 4, 4], got {tuple(gt_pose.shape)}")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError(f"verts must be [V, 3] with V >= 1, got {tuple(verts.shape)}")
+    if syms.dim() != 3 or tuple(syms.shape[1:]) != (4, 4) or not 1 <= syms.shape[0] <= SCORE_MAX_SYMS:
+        raise ValueError(f"syms must be [K, 4, 4] with 1 <= K <= {SCORE_MAX_SYMS}, got {tuple(syms.shape)}")
+    if gt_offs.numel() < 1:
+        raise ValueError("gt_offs: expected one entry per capture and one more")
+    n_end, n_out, S = row0 + n_rows, n_rows * g_max, gt_offs.numel() - 1
+    rows = [(pose, "pose", f64, 16 * n_end, AT_LEAST), (scene, "scene", i32, n_end, AT_LEAST),
+            (gt_pose, "gt_pose", f64, None, ANY), (gt_offs, "gt_offs", i64, S + 1, EXACT),
+            (verts, "verts", f64, None, ANY), (syms, "syms", f64, None, ANY),
+            (err, "err", f64, n_out, EXACT), (sym, "sym", i32, n_out, EXACT)]
+    if t_err is not None:
+        rows.append((t_err, "t_err", f64, n_out, EXACT))
+    if rot_cos is not None:
+        rows.append((rot_cos, "rot_cos", f64, n_out, EXACT))
+    ops._check_args(dev, rows)
+    if n_rows == 0:
+        return                       # no row: nothing to launch
+    if gt_pose.shape[0] == 0:
+        raise ValueError("gt_pose holds no pose")
+    ops._call("mvm_score_poses", ops._p(pose), ops._p(scene), scene_base, ops._p(gt_pose), ops._p(gt_offs), S,
+              g_max, ops._p(verts), int(verts.shape[0]), ops._p(syms), int(syms.shape[0]), row0, n_rows,
+              ops._p(err), ops._p(sym), ops._p(t_err), ops._p(rot_cos), ops._stream(pose))
+
+
+@ops._gpu_op("match_scores_out", ("gt_index", "tp"), namespace="mvmatch_views")
+def match_scores_out(err: Tensor, row_offs: Tensor, gt_offs: Tensor, thresholds: List[float], gt_index: Tensor,
+                     tp: Tensor) -> None:
+    """Every capture's rows matched greedily to its ground truth, once per
+    threshold (mvm_match_scores).  ``err`` / ``row_offs`` / ``gt_offs`` are
+    read only; ``gt_index`` / ``tp`` out."""
+    dev = ops._gpu(err, "err", "score matcher")
+    if err.dim() != 2:
+        raise ValueError(f"err must be [n, g_max], got {tuple(err.shape)}")
+    n, g_max, T, S = int(err.shape[0]), int(err.shape[1]), len(thresholds), row_offs.numel() - 1
+    if not 1 <= g_max <= SCORE_MAX_MATCH_GT:
+        raise ValueError(f"err: expected 1..{SCORE_MAX_MATCH_GT} ground-truth columns (g_max), got {g_max}")
+    if not 1 <= T <= SCORE_MAX_THRESHOLDS:
+        raise ValueError(f"thresholds: expected 1..{SCORE_MAX_THRESHOLDS} values, got {T}")
+    if any(math.isnan(v) for v in thresholds):
+        raise ValueError("thresholds: a NaN is no threshold")
+    if S < 0:
+        raise ValueError("row_offs: expected one entry per capture and one more")
+    ops._check_args(dev, [(err, "err", f64, n * g_max, EXACT), (row_offs, "row_offs", i64, S + 1, EXACT),
+                          (gt_offs, "gt_offs", i64, S + 1, EXACT), (gt_index, "gt_index", i32, T * n, EXACT),
+                          (tp, "tp", i32, T * S, EXACT)])
+    if n == 0 and S == 0:
+        return                       # no row and no capture: nothing to write
+    ops._call("mvm_match_scores", ops._p(err), g_max, ops._p(row_offs), ops._p(gt_offs), S,
+              (ctypes.c_double * T)(*thresholds), T, ops._p(gt_index), ops._p(tp), n, ops._stream(err))
+
+
 def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
               seed=(0, 1, 2), sub_cam_offs: Optional[Tensor] = None, orig: Optional[Tensor] = None) -> Tensor:
     """Flag the detections the matches of one pass hold (device).
@@ -525,3 +601,140 @@ def fuse_rotations(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs, n_
                                                fuse, cam, out.rot_views, out.R, out.pose, out.spread,
                                                out.slot_status, out.row_status)
     return out
+
+
+@dataclass
+class PoseScores:
+    """What ``score_poses`` returns, on the device (n rows, Gmax ground-truth columns)."""
+    err: Tensor                  # float64 [n, Gmax]   MSSD of (row, the capture's g-th object); +inf where sym < 0
+    sym: Tensor                  # int32 [n, Gmax]     the symmetry that gave it, or SYM_PADDING (g is past the
+    #                                                  capture's objects), SYM_NO_CAPTURE, SYM_NOT_FINITE
+    t_err: Tensor                # float64 [n, Gmax]   the distance of the translations; +inf where sym < 0
+    rot_cos: Tensor              # float64 [n, Gmax]   the cosine of the rotation between the two; NaN where sym < 0
+    # set by MatchTable.score(thresholds=...): ``match_scores`` of err
+    gt_index: Optional[Tensor] = None     # int32 [T, n]   the object each row took per threshold, or -1
+    tp: Optional[Tensor] = None           # int32 [T, S]   matched rows per threshold and capture
+
+
+def _host_offsets(offs, name: str) -> np.ndarray:
+    """An offset table (host array, sequence or tensor) as a checked host int64 array."""
+    if isinstance(offs, Tensor):
+        offs = offs.detach().cpu().numpy()
+    offs = np.ascontiguousarray(offs, np.int64).reshape(-1)
+    if offs.size < 1 or offs[0] < 0 or (np.diff(offs) < 0).any():
+        raise ValueError(f"{name}: expected non-decreasing offsets from 0 on, one per capture and one more")
+    return offs
+
+
+def _model_array(a, name: str, tail: tuple, dev) -> Tensor:
+    """Vertices or symmetries: a device tensor taken as given, or a host array
+    checked (finite and below 2^200 in magnitude) and copied."""
+    if isinstance(a, Tensor):
+        return a.contiguous()
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != len(tail) + 1 or a.shape[1:] != tail or a.shape[0] < 1:
+        raise ValueError(f"{name} must be [k, {', '.join(str(t) for t in tail)}] with k >= 1, got {a.shape}")
+    if not (np.abs(a) < SCORE_POSE_MAX).all():
+        raise ValueError(f"{name}: expected finite values below 2^200 in magnitude")
+    return torch.from_numpy(a).to(dev)
+
+
+def score_poses(pose: Tensor, scene: Tensor, gt_pose, gt_offs, verts, syms=None,
+                rows: Optional[Sequence[int]] = None, scene_base: int = 0) -> PoseScores:
+    """The BOP pose error MSSD (maximum symmetry-aware surface distance) of
+    every (estimate, ground-truth object) pair of a capture (device; DESIGN
+    §3.20).  ``pose`` f64 [n, 4, 4]: the estimates in the world frame (for
+    example ``FusedRotations.pose``) and ``scene`` int32 [n] their capture ids,
+    neither written; ``gt_pose`` f64 [G, 4, 4] the ground-truth poses in the
+    world frame and ``gt_offs`` int64 [S + 1] the rows of each capture among
+    them (host arrays, copied once, or device tensors; ``gt_offs`` is read on
+    the host either way: its largest count is the width of the result);
+    ``verts`` f64 [V, 3] the model's vertices and ``syms`` f64 [K, 4, 4] (K <=
+    64, default the identity) its symmetry transforms (host arrays are checked:
+    finite and below 2^200).  For every row of ``rows`` ((begin, end), default
+    all) and every g < Gmax: ``err = min_k max_v |(Rp v + tp) - (Rg (Sk v + sk)
+    + tg)|`` in the affine form tests/score_model.py states; the result is its
+    bits.
+    -> ``PoseScores``; ``sym`` is the symmetry of the minimum (the lowest of
+    equal ones), SYM_NO_CAPTURE where ``scene - scene_base`` is no capture of
+    ``gt_offs``, SYM_PADDING where g is past the capture's objects,
+    SYM_NOT_FINITE where either pose has a read entry that is not below 2^200
+    in magnitude; in all three ``err`` and ``t_err`` are +inf and ``rot_cos``
+    NaN.  The arccosine of ``rot_cos`` is the caller's."""
+    dev = pose.device
+    n = int(scene.shape[0])
+    if rows is None:
+        rows = (0, n)
+    try:
+        begin, end = (int(r) for r in rows)
+    except (TypeError, ValueError):
+        raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+    if not 0 <= begin <= end <= n:
+        raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+    offs = _host_offsets(gt_offs, "gt_offs")
+    if not isinstance(gt_pose, Tensor):
+        gt_pose = torch.from_numpy(np.ascontiguousarray(gt_pose, np.float64).reshape(-1, 4, 4)).to(dev)
+    if gt_pose.dim() != 3 or tuple(gt_pose.shape[1:]) != (4, 4):
+        raise ValueError(f"gt_pose must be [G, 4, 4], got {tuple(gt_pose.shape)}")
+    if offs[-1] > gt_pose.shape[0]:
+        raise ValueError(f"gt_offs ends at {offs[-1]}, gt_pose holds {gt_pose.shape[0]} poses")
+    if gt_pose.shape[0] == 0:            # no object anywhere: a pose no offset reaches
+        gt_pose = torch.zeros((1, 4, 4), dtype=f64, device=gt_pose.device)
+    g_max = max(1, int(np.diff(offs).max())) if offs.size > 1 else 1
+    verts = _model_array(verts, "verts", (3,), dev)
+    syms = _model_array(np.eye(4)[None] if syms is None else syms, "syms", (4, 4), dev)
+    m = end - begin
+    e = lambda dt: torch.empty((m, g_max), dtype=dt, device=dev)
+    out = PoseScores(err=e(f64), sym=e(i32), t_err=e(f64), rot_cos=e(f64))
+    offs_dev = gt_offs if isinstance(gt_offs, Tensor) and gt_offs.device == dev and gt_offs.dtype == i64 \
+        else torch.from_numpy(offs).to(dev)
+    torch.ops.mvmatch_views.score_poses_out(pose.contiguous(), scene.contiguous(), gt_pose.contiguous(),
+                                            offs_dev.contiguous(), verts, syms, int(scene_base), g_max, begin, m,
+                                            out.err, out.sym, out.t_err, out.rot_cos)
+    return out
+
+
+def match_scores(err: Tensor, row_offs, gt_offs, thresholds):
+    """Match every capture's rows greedily to its ground truth (device; DESIGN
+    §3.20).  ``err`` f64 [n, Gmax <= 1024]: ``score_poses``'s err over the
+    whole table, not written; ``row_offs`` int64 [S + 1]: a ``MatchTable``'s
+    ``offs``; ``gt_offs`` int64 [S + 1] as ``score_poses`` takes it (host
+    arrays or tensors; both are checked on the host); ``thresholds`` 1..16
+    numbers, no NaN.  Per threshold and capture the rows are walked in table
+    order -- the matcher's cost order, the confidence order BOP's greedy
+    matching wants --, and a row takes the free object with the smallest error
+    below the threshold (strict; the lowest index wins a tie) or -1.
+    -> (gt_index int32 [T, n], tp int32 [T, S]: the matched rows per threshold
+    and capture).  Rows outside every capture get -1."""
+    ro, go = _host_offsets(row_offs, "row_offs"), _host_offsets(gt_offs, "gt_offs")
+    if ro.size != go.size:
+        raise ValueError(f"row_offs describes {ro.size - 1} captures, gt_offs {go.size - 1}")
+    if err.dim() != 2:
+        raise ValueError(f"err must be [n, g_max], got {tuple(err.shape)}")
+    n, dev = int(err.shape[0]), err.device
+    if ro[-1] > n:
+        raise ValueError(f"row_offs ends at {ro[-1]}, err holds {n} rows")
+    try:
+        thresholds = [float(v) for v in thresholds]
+    except TypeError:
+        raise ValueError(f"thresholds: expected 1..{SCORE_MAX_THRESHOLDS} numbers, got {thresholds!r}") from None
+    if not 1 <= len(thresholds) <= SCORE_MAX_THRESHOLDS or any(math.isnan(v) for v in thresholds):
+        raise ValueError(f"thresholds: expected 1..{SCORE_MAX_THRESHOLDS} numbers and no NaN, got {thresholds}")
+    T, S = len(thresholds), ro.size - 1
+    gt_index = torch.empty((T, n), dtype=i32, device=dev)
+    tp = torch.empty((T, S), dtype=i32, device=dev)
+    torch.ops.mvmatch_views.match_scores_out(err.contiguous(), torch.from_numpy(ro).to(dev),
+                                             torch.from_numpy(go).to(dev), thresholds, gt_index, tp)
+    return gt_index, tp
+
+
+def recall_precision(tp: Tensor, row_offs, gt_offs):
+    """-> (recall f64 [T], precision f64 [T]) of ``match_scores``'s ``tp`` over
+    the whole table, on ``tp``'s device: the matched rows over the ground-truth
+    objects and over the table's rows (NaN where there are none).  Average
+    recall is the mean of ``recall`` over the thresholds."""
+    as_t = lambda o: o if isinstance(o, Tensor) else torch.from_numpy(np.ascontiguousarray(o, np.int64))
+    n_rows = as_t(row_offs).diff().sum().to(tp.device, f64)
+    n_gt = as_t(gt_offs).diff().sum().to(tp.device, f64)
+    hit = tp.sum(dim=1).to(f64)
+    return hit / n_gt, hit / n_rows

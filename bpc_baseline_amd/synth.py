@@ -28,7 +28,7 @@ import numpy as np
 from .inference.utils.camera_utils import (calc_pose_matrix, camera_pairs,
                                            fundamental_matrices_batched)
 
-__all__ = ["IPD_K", "SceneBatch", "make_rig", "make_capture", "make_scenes"]
+__all__ = ["IPD_K", "SceneBatch", "make_rig", "make_capture", "make_capture_gt", "make_scenes"]
 
 # blog/documentation.md:71 (scene_camera_cam1.json example)
 IPD_K = np.array([[4209.025366776721, 0.0, 1200.0],
@@ -74,6 +74,12 @@ def _project(K: np.ndarray, RT: np.ndarray, X: np.ndarray) -> np.ndarray:
 
 def _views(rng: np.random.Generator, Ks, RTs, counts, *, box_px: float, noise_px: float):
     """Per-camera integer boxes and half-integer centres (arrays)."""
+    return _views_gt(rng, Ks, RTs, counts, box_px=box_px, noise_px=noise_px)[0]
+
+
+def _views_gt(rng: np.random.Generator, Ks, RTs, counts, *, box_px: float, noise_px: float):
+    """``_views`` and the object centres X f64 [n_obj, 3] it projects (camera c
+    sees the first ``min(counts[c] // 2, n_obj)`` of them)."""
     n_obj = max(counts) // 2 if counts else 0
     X = np.stack([rng.uniform(-250, 250, n_obj), rng.uniform(-250, 250, n_obj),
                   rng.uniform(-80, 80, n_obj)], axis=1)
@@ -88,7 +94,7 @@ def _views(rng: np.random.Generator, Ks, RTs, counts, *, box_px: float, noise_px
         boxes = np.trunc(np.concatenate([centres - half, centres + half], axis=1)).astype(np.int64)
         cxy = 0.5 * (boxes[:, 0:2] + boxes[:, 2:4])          # process_pose.py:135-136
         views.append((boxes, cxy.astype(np.float64)))
-    return views
+    return views, X
 
 
 def make_capture(rng: np.random.Generator, n_cams: int, n_dets, *, box_px: float = 80.0,
@@ -102,15 +108,24 @@ def make_capture(rng: np.random.Generator, n_cams: int, n_dets, *, box_px: float
     repeats the first few detections of every view (exact ties for the argmin
     and Hungarian tests).
     """
+    return make_capture_gt(rng, n_cams, n_dets, box_px=box_px, noise_px=noise_px, duplicates=duplicates)[:3]
+
+
+def make_capture_gt(rng: np.random.Generator, n_cams: int, n_dets, *, box_px: float = 80.0,
+                    noise_px: float = 1.5, duplicates: int = 0):
+    """``make_capture`` with its ground truth: ``(Ks, RTs, detections, X)``, X
+    f64 [n_obj, 3] the object centres in the world frame whose projections
+    are the true half of every view.  Same draws, same first three results."""
     counts = [int(n_dets)] * n_cams if np.isscalar(n_dets) else [int(n) for n in n_dets]
     Ks, RTs = make_rig(rng, n_cams)
     detections: Dict[int, List[dict]] = {}
-    for c, (boxes, cxy) in enumerate(_views(rng, Ks, RTs, counts, box_px=box_px, noise_px=noise_px)):
+    views, X = _views_gt(rng, Ks, RTs, counts, box_px=box_px, noise_px=noise_px)
+    for c, (boxes, cxy) in enumerate(views):
         dets = [{"bbox": tuple(int(v) for v in b), "bb_center": (float(x), float(y))}
                 for b, (x, y) in zip(boxes, cxy)]
         dets.extend(dict(d) for d in dets[:duplicates])
         detections[c] = dets
-    return Ks, RTs, detections
+    return Ks, RTs, detections, X
 
 
 @dataclass

@@ -56,6 +56,8 @@ extern "C" {
                            changed) */
 #define MVM_HAS_POSES 1 /* mvm_fuse_rotations: an addition to ABI 8 (no existing signature or
                            struct changed) */
+#define MVM_HAS_SCORES 1 /* mvm_score_poses, mvm_match_scores: additions to ABI 8 (no existing
+                            signature or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -969,6 +971,85 @@ int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev
                        int32_t fuse_cam, double *rot_views_dev, double *R_dev, double *pose_dev,
                        double *spread_dev, int32_t *slot_status_dev, int32_t *row_status_dev,
                        mvm_stream_t stream);
+
+/*
+ * Poses against ground truth (additions to ABI 8, announced by
+ * MVM_HAS_SCORES).  tests/score_model.py states every
+ * step of both; the kernels return its bits.
+ *
+ * mvm_score_poses: the BOP pose error MSSD (maximum symmetry-aware surface
+ * distance) of every (estimate, ground-truth object) pair of a capture.
+ * Inputs, none written:
+ *   pose_dev     f64 [>= row0 + n_rows, 4, 4] and scene_dev int32 [same]: the
+ *                estimates in the world frame and each one's capture id;
+ *   gt_pose_dev  f64 [G, 4, 4]: the ground-truth poses in the world frame;
+ *   gt_offs_dev  int64 [n_scenes + 1]: capture s owns ground-truth rows
+ *                gt_offs[s] : gt_offs[s + 1] (non-decreasing, within 0 .. G: it
+ *                is trusted as every offset table here is);
+ *   verts_dev    f64 [n_verts, 3] and syms_dev f64 [n_syms, 4, 4]: the model's
+ *                vertices and its symmetry transforms, finite and below 2^200
+ *                in magnitude.
+ * Only the top three rows of a pose or a symmetry are read.  For row r of the
+ * n_rows rows from row0, s = scene - scene_base, and column g < g_max, each
+ * rule applying only where the one before did not:
+ *   s is no index < n_scenes     err = t_err = +inf, rot_cos = NaN, sym = -2;
+ *   g >= capture s's row count   the same with sym = -1 (padding);
+ *   one of the 12 read entries of either pose is not below 2^200 in magnitude
+ *   (a NaN is not)               the same with sym = -3;
+ *   otherwise, with (Rp, tp) the estimate, (Rg, tg) the ground truth and
+ *   (Sk, sk) symmetry k: M = Rg Sk, A = Rp - M, b = tp - (Rg sk + tg),
+ *   m_k = max over the vertices v of |A v + b|^2; sym = the lowest k with the
+ *   smallest m_k, err = sqrt(m_sym), t_err = |tp - tg|, rot_cos =
+ *   (sum_ij Rp_ij M_sym_ij - 1) / 2 (the cosine of the rotation between the
+ *   two; its arccosine is the caller's).  Products, sums and square roots are
+ *   single float64 operations in the model's order, nothing contracted.
+ * Outputs, [n_rows, g_max] each, every entry written: err_dev f64, sym_dev
+ * int32, t_err_dev f64 (may be NULL) and rot_cos_dev f64 (may be NULL).  One
+ * launch on `stream`, a thread per pair; no allocation, copy or
+ * synchronisation.  n_rows == 0 is MVM_OK whatever the other arguments are.
+ * Refused before the launch: a NULL pointer other than t_err_dev and
+ * rot_cos_dev; n_syms outside 1..64; n_verts < 1; g_max < 1; a negative row0,
+ * n_rows or n_scenes; more pairs than one grid holds (n_rows g_max >= 2^32:
+ * split the rows).
+ */
+int mvm_score_poses(const double *pose_dev, const int32_t *scene_dev, int32_t scene_base,
+                    const double *gt_pose_dev, const int64_t *gt_offs_dev, int32_t n_scenes,
+                    int32_t g_max, const double *verts_dev, int32_t n_verts, const double *syms_dev,
+                    int32_t n_syms, int64_t row0, int64_t n_rows, double *err_dev, int32_t *sym_dev,
+                    double *t_err_dev /* may be NULL */, double *rot_cos_dev /* may be NULL */,
+                    mvm_stream_t stream);
+
+/*
+ * mvm_match_scores: the greedy matching of each capture's rows to its ground
+ * truth, once per threshold.  Inputs, none written:
+ *   err_dev          f64 [n_rows_total, g_max]: mvm_score_poses's err over the
+ *                    whole table;
+ *   row_offs_dev     int64 [n_scenes + 1]: capture s owns table rows
+ *                    row_offs[s] : row_offs[s + 1] (non-decreasing);
+ *   gt_offs_dev      int64 [n_scenes + 1]: as above; only the counts are read;
+ *   thresholds_host  n_thresholds values on the host, copied into the kernel's
+ *                    arguments (never dereferenced on the device).
+ * For threshold t and capture s the rows are walked in table order; row r takes
+ * the not-yet-taken g < min(count of s, g_max) with the smallest err[r][g]
+ * among those with err[r][g] < thresholds[t] (strict; the lowest g wins a tie),
+ * or -1.  +inf and NaN never match.  Outputs:
+ *   gt_index_dev  int32 [n_thresholds, n_rows_total]: the g taken, or -1; the
+ *                 rows no capture owns are written -1 by the same launch;
+ *   tp_dev        int32 [n_thresholds, n_scenes]: the rows of s that took one.
+ * Every offset read from row_offs is clamped into 0 .. n_rows_total (and an
+ * end below its begin up to it) before a row is touched, and a count into
+ * 0 .. g_max.  One launch on `stream`, a wave per (capture, threshold); no
+ * allocation, copy or synchronisation.  n_scenes == 0 with n_rows_total == 0 is
+ * MVM_OK whatever the other arguments are.  Refused before the launch: g_max
+ * outside 1..1024 (MVM_ERR_UNSUPPORTED); n_thresholds outside 1..16; a
+ * negative n_scenes or n_rows_total; a NULL pointer that would be read or
+ * written (err_dev and gt_index_dev may be NULL without rows, row_offs_dev,
+ * gt_offs_dev and tp_dev without captures).
+ */
+int mvm_match_scores(const double *err_dev, int32_t g_max, const int64_t *row_offs_dev,
+                     const int64_t *gt_offs_dev, int32_t n_scenes, const double *thresholds_host,
+                     int32_t n_thresholds, int32_t *gt_index_dev, int32_t *tp_dev,
+                     int64_t n_rows_total, mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory

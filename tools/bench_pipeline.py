@@ -29,6 +29,11 @@ cameras, fuse="mean"; the stage time (host clock around the launch and one
 synchronise, median of --steps) is in the line, beside the same work done on the
 host one row at a time through tests/pose_model.py, timed on --cpu-sample rows
 and scaled to the table.
+--score (with --cams C > 3): the batch's table against the synthetic object
+centres through MatchTable.score: centre distances of every
+(row, object) pair of a capture and the greedy matching at --score-thresholds
+(mm); recall, precision and the stage time (host clock around the two launches
+and one synchronise, median of --steps) are in the line.
 """
 import argparse
 import json
@@ -66,15 +71,18 @@ def cpu_chain(b, s):
     return m, X
 
 
-def wide_batch(captures, dets, C, seed=5):
+def wide_batch(captures, dets, C, seed=5, centres=None):
     """Detector outputs of `captures` C-camera captures (make_capture: half of
     every view true objects, half clutter), capture s from default_rng(seed + s)
-    -> (boxes f32 [n, 4], conf, cls, img_offs i64 [C S + 1], Ks, RTs)."""
-    from bpc_baseline_amd.synth import make_capture
+    -> (boxes f32 [n, 4], conf, cls, img_offs i64 [C S + 1], Ks, RTs).
+    ``centres``: a list that gets every capture's object centres f64 [n_obj, 3]."""
+    from bpc_baseline_amd.synth import make_capture_gt
     boxes, counts = [], []
     Ks, RTs = np.empty((captures, C, 3, 3), np.float32), np.empty((captures, C, 4, 4))
     for s in range(captures):
-        k, rt, det = make_capture(np.random.default_rng(seed + s), C, dets)
+        k, rt, det, X = make_capture_gt(np.random.default_rng(seed + s), C, dets)
+        if centres is not None:
+            centres.append(X)
         Ks[s], RTs[s] = np.stack(k), np.stack(rt)
         for c in range(C):
             boxes.append(np.array([d["bbox"] for d in det[c]], np.float32).reshape(-1, 4))
@@ -177,13 +185,46 @@ def bench_poses(res, args, dev, RTs):
     return out
 
 
+def bench_score(res, args, dev, centres):
+    """--score: the batch's table against the captures' object centres through
+    MatchTable.score -> the line's "score" entry."""
+    from bpc_baseline_amd import ops_views
+    tab = res.table_all() if res.passes else res.table(reproj=True)
+    n = int(tab.offs[-1])
+    gt_offs = np.concatenate([[0], np.cumsum([len(X) for X in centres])]).astype(np.int64)
+    gt = np.tile(np.eye(4), (int(gt_offs[-1]), 1, 1))
+    gt[:, :3, 3] = np.concatenate(centres)
+    gt_dev = torch.from_numpy(gt).to(dev)
+    thresholds = list(args.score_thresholds)
+    for _ in range(3):
+        got = tab.score(gt_dev, gt_offs, thresholds=thresholds)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(args.steps):
+        t0 = time.perf_counter()
+        got = tab.score(gt_dev, gt_offs, thresholds=thresholds)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    recall, precision = ops_views.recall_precision(got.tp, tab.offs, gt_offs)
+    return {"rows": n, "objects": int(gt_offs[-1]), "g_max": int(got.err.shape[1]), "thresholds_mm": thresholds,
+            "recall": [round(v, 6) for v in recall.tolist()],
+            "precision": [round(v, 6) for v in precision.tolist()],
+            "average_recall": round(float(recall.mean()), 6),
+            "stage_ms": float(np.median(times)) * 1e3, "stage_ms_all_steps": [round(t * 1e3, 4) for t in times],
+            "note": "identity rotations at the table's X against the synthetic centres, one origin vertex: err is "
+                    "the centre distance; host clock around the score and match launches and one device "
+                    "synchronise; the estimates' assembly, the offsets' upload and the allocation of the outputs "
+                    "are inside the stage"}
+
+
 def main_wide(args):
     """--cams C > 3: ms per batch and synchronised stage times of
     match_captures(n_cams=C), or (--first-three) of the three-camera chain on
     cameras 0-2 of the same captures."""
     dev = torch.device("cuda", 0)
     C = args.cams
-    boxes, conf, cls, offs, Ks, RTs = wide_batch(args.captures, args.dets, C)
+    centres = [] if args.score else None
+    boxes, conf, cls, offs, Ks, RTs = wide_batch(args.captures, args.dets, C, centres=centres)
     kw = dict(keep_cube=args.keep_cube, rig=args.rig)
     if args.first_three:
         rows = np.concatenate([np.arange(offs[C * s], offs[C * s + 3]) for s in range(args.captures)])
@@ -243,6 +284,8 @@ def main_wide(args):
         out["crops"] = bench_crops(res, args, dev)
     if args.poses is not None:
         out["poses"] = bench_poses(res, args, dev, RTs)
+    if args.score:
+        out["score"] = bench_score(res, args, dev, centres)
     print(json.dumps(out))
 
 
@@ -271,6 +314,11 @@ def main():
     ap.add_argument("--crop-dtype", choices=("float32", "float16"), default="float32")
     ap.add_argument("--poses", choices=("euler", "quat", "6d", "all"), default=None, metavar="MODE",
                     help="with --cams C > 3: MatchTable.poses over the table, fuse=\"mean\" (DESIGN §3.19)")
+    ap.add_argument("--score", action="store_true",
+                    help="with --cams C > 3: MatchTable.score of the table against the synthetic centres (DESIGN §3.20)")
+    ap.add_argument("--score-thresholds", type=lambda v: tuple(float(x) for x in v.split(",")),
+                    default=(1.0, 2.0, 5.0, 10.0), metavar="a[,b...]",
+                    help="with --score: the centre-distance thresholds, mm")
     ap.add_argument("--captures", type=int, default=1000)
     ap.add_argument("--dets", type=int, default=24)
     ap.add_argument("--steps", type=int, default=5)
@@ -292,6 +340,8 @@ def main():
         ap.error("--crops needs --cams C > 3 without --first-three, and ROWS >= 1")
     if args.poses is not None and (args.cams == 3 or args.first_three):
         ap.error("--poses needs --cams C > 3 without --first-three")
+    if args.score and (args.cams == 3 or args.first_three):
+        ap.error("--score needs --cams C > 3 without --first-three")
     if args.cams > 3:
         return main_wide(args)
     dev = torch.device("cuda", 0)
