@@ -230,6 +230,14 @@ SIGNATURES = {
         _vp, _i32, _vp, _vp, _i32,          # err, g_max, row_offs, gt_offs, n_scenes
         _vp, _i32,                          # thresholds (host), n_thresholds
         _vp, _vp, _i64, _vp]),              # gt_index, tp (out), n_rows_total, stream
+    "mvm_fuse_rotations_sym": (ctypes.c_int, [
+        _vp, _i32, _vp, _i32,               # raw, D, scene, scene_base
+        _vp, _vp, _vp, _i32, _i32,          # views, X, RTs, n_scenes, n_cams
+        _i64, _i64, _vp, _i32, _i32,        # row0, n_rows, cams (host), n_sel, mode
+        _vp, _i32, _i32,                    # syms, n_syms, rounds
+        _vp, _vp, _vp, _vp, _vp, _vp,       # rot_views (may be NULL), R, pose, spread (may be NULL), slot_status, row_status (out)
+        _vp, _vp, _vp,                      # sym_index, sym_margin (may be NULL), n_changed (may be NULL) (out)
+        _vp]),                              # stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

@@ -6,6 +6,8 @@
 // largest eigenvector of Horn's 4 x 4 matrix by cyclic Jacobi rotations).
 // Every step and its order are stated by tests/pose_model.py, whose bits the
 // kernel returns.
+// fuse_rotations_sym_kernel takes the same mean under the object's symmetries
+// (tests/pose_sym_model.py).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -21,7 +23,8 @@ namespace {
 
 enum : int { kModeEuler = 0, kModeQuat = 1, kMode6d = 2 };
 enum : int { kFuseCam = 0, kFuseMean = 1 };
-enum : int32_t { kSlotNoView = 1, kSlotNoCapture = 2, kSlotDegenerate = 4 };
+enum : int32_t { kSlotNoView = 1, kSlotNoCapture = 2, kSlotDegenerate = 4, kSlotNoSym = 8 };
+constexpr int kMaxRounds = 4;
 enum : int32_t { kRowNoRotation = 1, kRowAmbiguous = 2 };
 
 constexpr int kJacobiSweeps = 8;
@@ -336,18 +339,203 @@ __global__ __launch_bounds__(kThreads) void fuse_rotations_kernel(
     P[12] = 0.0, P[13] = 0.0, P[14] = 0.0, P[15] = 1.0;
 }
 
-}  // namespace
+// ---- the mean under the object's symmetries (tests/pose_sym_model.py) ----
 
-extern "C" {
+// W S for the top-left 3 x 3 block of the row-major 4 x 4 symmetry S
+__device__ __forceinline__ void apply_symmetry(const double W[9], const double *__restrict__ S, double Wp[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            Wp[3 * i + j] = (W[3 * i] * S[j] + W[3 * i + 1] * S[4 + j]) + W[3 * i + 2] * S[8 + j];
+}
 
-int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev, int32_t scene_base,
-                       const int32_t *views_dev, const double *X_dev, const double *RTs_dev, int32_t n_scenes,
-                       int32_t n_cams, int64_t row0, int64_t n_rows, const int32_t *cams_host, int32_t n_sel,
-                       int32_t mode, int32_t fuse, int32_t fuse_cam, double *rot_views_dev, double *R_dev,
-                       double *pose_dev, double *spread_dev, int32_t *slot_status_dev, int32_t *row_status_dev,
-                       mvm_stream_t stream) {
-    mvm_clear_error();
-    if (n_rows == 0) return MVM_OK;
+// The symmetry that takes W nearest Rref: B = Rref^T W, s_k = sum_ij B_ij S_k,ji
+// (the trace of B S_k) over ascending k; strict '>' from -inf keeps the lowest index of a tie and
+// never takes a NaN.  Every lane walks the same k, so a symmetry is read at a
+// wave-uniform address (scalar loads).  -> the index or -1, and best - second.
+__device__ __forceinline__ int32_t nearest_symmetry(const double Rref[9], const double W[9],
+                                                    const double *__restrict__ syms, int32_t n_syms,
+                                                    double &margin) {
+    double B[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            B[3 * i + j] = (Rref[i] * W[j] + Rref[3 + i] * W[3 + j]) + Rref[6 + i] * W[6 + j];
+    double best = -INFINITY, second = -INFINITY;
+    int32_t kb = -1;
+#pragma unroll 1
+    for (int32_t k = 0; k < n_syms; ++k) {
+        const double *__restrict__ S = syms + (int64_t)k * 16;
+        double s = B[0] * S[0];
+        s = s + B[1] * S[4];
+        s = s + B[2] * S[8];
+#pragma unroll
+        for (int i = 1; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s = s + B[3 * i + j] * S[4 * j + i];
+        if (s > best) {
+            second = best, best = s, kb = k;
+        } else if (s > second) {
+            second = s;
+        }
+    }
+    margin = best - second;
+    return kb;
+}
+
+// The row's fused rotation, into R_out and the pose's block, and its two
+// counts; n_changed first: where it is not wanted it lies on row_status
+__device__ __forceinline__ void store_row(const double Rr[9], int32_t rstat, int32_t changed, double *Ro,
+                                          double *P, int32_t *row_status, int32_t *n_changed) {
+    *n_changed = changed;
+    *row_status = rstat;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Ro[3 * i + j] = Rr[3 * i + j];
+            P[4 * i + j] = Rr[3 * i + j];
+        }
+}
+
+// One thread per row of the range.  Each round walks the row's slots: a usable
+// slot's world rotation is computed anew, aligned to the reference by its
+// nearest symmetry and added to the sum; the mean of the round is the next
+// round's reference.  What a slot took and whether it is still usable live in
+// the thread's own sym_index / slot_status outputs between the rounds, so no
+// per-slot array exists to be indexed.
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void fuse_rotations_sym_kernel(
+    const float *__restrict__ raw, const int32_t *__restrict__ scene, int32_t scene_base,
+    const int32_t *__restrict__ views, const double *__restrict__ X, const double *__restrict__ RTs,
+    int32_t n_scenes, int32_t n_cams, int64_t row0, int64_t n_rows, uint32_t cams_packed, int32_t n_sel,
+    const double *__restrict__ syms, int32_t n_syms, int32_t rounds, double *__restrict__ rot_views,
+    double *__restrict__ R_out, double *__restrict__ pose, double *__restrict__ spread,
+    int32_t *slot_status, int32_t *__restrict__ row_status, int32_t *sym_index,
+    double *__restrict__ sym_margin, int32_t *__restrict__ n_changed) {
+    const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t t = row0 + r;
+    const int64_t sc = (int64_t)scene[t] - scene_base;
+    PoseRow row;
+    row.raw = raw + r * n_sel * mode_width(MODE);
+    row.views = views + t * n_cams;
+    row.rts = (sc >= 0 && sc < n_scenes) ? RTs + sc * n_cams * 16 : nullptr;
+    row.cams_packed = cams_packed;
+
+    // The row's own places in the outputs, taken once.  An optional output that
+    // is not wanted is written all the same, into the row's own R_out (whose
+    // nine entries hold a value per slot; the views go there with a slot stride
+    // of 0) or row_status, which the end of every walk writes after it:
+    // so the walks hold no test for the four, whose lane masks would otherwise
+    // stay in scalar registers that the Euler decoder needs for itself.
+    int32_t *const my_status = slot_status + r * n_sel, *const my_index = sym_index + r * n_sel;
+    int32_t *const my_row_status = row_status + r, *const my_changed = n_changed ? n_changed + r : my_row_status;
+    double *const Ro = R_out + r * 9, *const P = pose + r * 16;
+    double *const my_margin = sym_margin ? sym_margin + r * n_sel : Ro;
+    double *const my_views = rot_views ? rot_views + r * n_sel * 9 : Ro;
+    double *const my_spread = spread ? spread + r * n_sel : Ro;
+    const int views_step = rot_views ? 9 : 0;
+    // the pose's translation and last row wait for no rotation
+#pragma unroll
+    for (int i = 0; i < 3; ++i) P[4 * i + 3] = X[t * 3 + i];
+    P[12] = 0.0, P[13] = 0.0, P[14] = 0.0, P[15] = 1.0;
+
+    // the entry point has checked these: no loop below needs a guard for zero trips
+    __builtin_assume(n_sel >= 1 && n_sel <= MVM_MAX_CAMS);
+    __builtin_assume(n_syms >= 1);
+    __builtin_assume(rounds >= 1 && rounds <= kMaxRounds);
+    // what round 1 reads back as every later round does: every slot still in,
+    // no symmetry taken; and what a slot that ends unusable keeps: NaN
+    const double nan = __builtin_nan("");
+#pragma unroll 1
+    for (int k = 0; k < n_sel; ++k) {
+        my_status[k] = 0, my_index[k] = -1;
+        my_spread[k] = nan;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) my_views[k * views_step + e] = nan;
+    }
+
+    double Rr[9] = {}, W[9] = {}, Wp[9] = {};
+    bool have_ref = false;
+    int32_t rstat = 0, changed = 0;
+    // the rounds: align every usable slot to the reference, average, and leave
+    // the row as the round has it; the last round's is what stays
+#pragma unroll 1
+    for (int round = 0; round < rounds; ++round) {
+        double A[9] = {};
+        int n_here = 0;
+        int32_t changed_here = 0;
+#pragma unroll 1
+        for (int k = 0; k < n_sel; ++k) {
+            int32_t st = slot_world<MODE>(row, k, W);
+            if (st == 0) st = my_status[k];                            // lost to an earlier round
+            int32_t kb = -1;
+            double margin = nan;
+            if (st == 0) {
+                if (!have_ref) {                                       // round 1's reference: the first usable slot
+                    have_ref = true;
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) Rr[e] = W[e];
+                }
+                kb = nearest_symmetry(Rr, W, syms, n_syms, margin);
+                bool sane = kb >= 0;
+                if (sane) {
+                    apply_symmetry(W, syms + (int64_t)kb * 16, Wp);
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) sane = sane && below_world_max(Wp[e]);
+                }
+                if (sane) {
+                    ++n_here;
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) A[e] = A[e] + Wp[e];
+                    if (my_index[k] != kb) ++changed_here;
+                } else {
+                    st = kSlotNoSym, kb = -1, margin = nan;
+                }
+            }
+            my_status[k] = st;
+            my_index[k] = kb;
+            my_margin[k] = margin;
+        }
+        rstat = 0, changed = round > 0 ? changed_here : 0;
+        if (n_here == 0) {
+            rstat = kRowNoRotation;
+            round = rounds;                                            // every slot is lost: nothing left to align
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Rr[e] = nan;
+        } else {
+            double lam1, lam2;
+            mean_rotation(A, Rr, lam1, lam2);
+            if (lam1 - lam2 <= kAmbiguousGap * (double)n_here) rstat = kRowAmbiguous;
+        }
+        store_row(Rr, rstat, changed, Ro, P, my_row_status, my_changed);
+    }
+    // what needs the last mean: the aligned views and their distance to it
+#pragma unroll 1
+    for (int k = 0; k < n_sel; ++k) {
+        if (my_status[k] != 0) continue;
+        slot_world<MODE>(row, k, W);
+        apply_symmetry(W, syms + (int64_t)my_index[k] * 16, Wp);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) my_views[k * views_step + e] = Wp[e];
+        double s = 0.0;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+            const double d = Wp[e] - Rr[e];
+            s = s + d * d;
+        }
+        my_spread[k] = s;
+    }
+    // once more, behind whatever that walk wrote in the row's place
+    store_row(Rr, rstat, changed, Ro, P, my_row_status, my_changed);
+}
+
+// What both entry points refuse before their pointers
+int check_rotation_sizes(int32_t D, int32_t n_scenes, int32_t n_cams, int64_t row0, int64_t n_rows,
+                         int32_t n_sel, int32_t mode) {
     if (n_rows < 0 || row0 < 0)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "negative row0=%lld or n_rows=%lld", (long long)row0,
                         (long long)n_rows);
@@ -363,6 +551,42 @@ int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev
     if (D != mode_width(mode))
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "D=%d: mode=%d takes %d values per slot", D, mode,
                         mode_width(mode));
+    return MVM_OK;
+}
+
+// The selected cameras, four bits each
+int pack_cams(const int32_t *cams_host, int32_t n_sel, int32_t n_cams, uint32_t &cams_packed) {
+    cams_packed = 0;
+    for (int k = 0; k < n_sel; ++k) {
+        if (cams_host[k] < 0 || cams_host[k] >= n_cams)
+            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cams_host[%d]=%d is no camera < %d", k, cams_host[k],
+                            n_cams);
+        cams_packed |= (uint32_t)cams_host[k] << (4 * k);
+    }
+    return MVM_OK;
+}
+
+int row_grid(int64_t n_rows, int64_t &grid) {
+    grid = (n_rows + kThreads - 1) / kThreads;
+    if (grid > kMaxGridBlocks)
+        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_rows=%lld: more rows than one launch holds; split the rows",
+                        (long long)n_rows);
+    return MVM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev, int32_t scene_base,
+                       const int32_t *views_dev, const double *X_dev, const double *RTs_dev, int32_t n_scenes,
+                       int32_t n_cams, int64_t row0, int64_t n_rows, const int32_t *cams_host, int32_t n_sel,
+                       int32_t mode, int32_t fuse, int32_t fuse_cam, double *rot_views_dev, double *R_dev,
+                       double *pose_dev, double *spread_dev, int32_t *slot_status_dev, int32_t *row_status_dev,
+                       mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_rows == 0) return MVM_OK;
+    if (const int st = check_rotation_sizes(D, n_scenes, n_cams, row0, n_rows, n_sel, mode)) return st;
     if (fuse != kFuseCam && fuse != kFuseMean)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "fuse=%d: 0 (cam) or 1 (mean)", fuse);
     if (const int st = mvm_require_ptrs({{raw_dev, "raw_dev"},
@@ -376,21 +600,15 @@ int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev
                                          {slot_status_dev, "slot_status_dev"},
                                          {row_status_dev, "row_status_dev"}}))
         return st;                       // rot_views_dev and spread_dev may be NULL: not written
-    uint32_t cams_packed = 0;
+    uint32_t cams_packed;
+    if (const int st = pack_cams(cams_host, n_sel, n_cams, cams_packed)) return st;
     int fuse_k = -1;
-    for (int k = 0; k < n_sel; ++k) {
-        if (cams_host[k] < 0 || cams_host[k] >= n_cams)
-            return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "cams_host[%d]=%d is no camera < %d", k, cams_host[k],
-                            n_cams);
-        cams_packed |= (uint32_t)cams_host[k] << (4 * k);
-        if (fuse_k < 0 && cams_host[k] == fuse_cam) fuse_k = k;
-    }
+    for (int k = n_sel - 1; k >= 0; --k)
+        if (cams_host[k] == fuse_cam) fuse_k = k;                 // the first of equal ones
     if (fuse == kFuseCam && fuse_k < 0)
         return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "fuse_cam=%d is not among the selected cameras", fuse_cam);
-    const int64_t grid = (n_rows + kThreads - 1) / kThreads;
-    if (grid > kMaxGridBlocks)
-        return mvm_fail(MVM_ERR_UNSUPPORTED, "n_rows=%lld: more rows than one launch holds; split the rows",
-                        (long long)n_rows);
+    int64_t grid;
+    if (const int st = row_grid(n_rows, grid)) return st;
     dispatch_int<kModeEuler, kModeQuat, kMode6d>(mode, [&](auto m) {
         dispatch_bool(fuse == kFuseMean, [&](auto mean) {
             fuse_rotations_kernel<decltype(m)::value, decltype(mean)::value ? kFuseMean : kFuseCam>
@@ -401,6 +619,47 @@ int mvm_fuse_rotations(const float *raw_dev, int32_t D, const int32_t *scene_dev
         });
     });
     return mvm_check_launch("fuse_rotations_kernel");
+}
+
+int mvm_fuse_rotations_sym(const float *raw_dev, int32_t D, const int32_t *scene_dev, int32_t scene_base,
+                           const int32_t *views_dev, const double *X_dev, const double *RTs_dev,
+                           int32_t n_scenes, int32_t n_cams, int64_t row0, int64_t n_rows,
+                           const int32_t *cams_host, int32_t n_sel, int32_t mode, const double *syms_dev,
+                           int32_t n_syms, int32_t rounds, double *rot_views_dev, double *R_dev,
+                           double *pose_dev, double *spread_dev, int32_t *slot_status_dev,
+                           int32_t *row_status_dev, int32_t *sym_index_dev, double *sym_margin_dev,
+                           int32_t *n_changed_dev, mvm_stream_t stream) {
+    mvm_clear_error();
+    if (n_rows == 0) return MVM_OK;
+    if (const int st = check_rotation_sizes(D, n_scenes, n_cams, row0, n_rows, n_sel, mode)) return st;
+    if (n_syms < 1) return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "n_syms=%d: at least 1", n_syms);
+    if (rounds < 1 || rounds > kMaxRounds)
+        return mvm_fail(MVM_ERR_INVALID_ARGUMENT, "rounds=%d outside [1, %d]", rounds, kMaxRounds);
+    if (const int st = mvm_require_ptrs({{raw_dev, "raw_dev"},
+                                         {scene_dev, "scene_dev"},
+                                         {views_dev, "views_dev"},
+                                         {X_dev, "X_dev"},
+                                         {RTs_dev, "RTs_dev"},
+                                         {cams_host, "cams_host"},
+                                         {syms_dev, "syms_dev"},
+                                         {R_dev, "R_dev"},
+                                         {pose_dev, "pose_dev"},
+                                         {slot_status_dev, "slot_status_dev"},
+                                         {row_status_dev, "row_status_dev"},
+                                         {sym_index_dev, "sym_index_dev"}}))
+        return st;       // rot_views_dev, spread_dev, sym_margin_dev and n_changed_dev may be NULL: not written
+    uint32_t cams_packed;
+    if (const int st = pack_cams(cams_host, n_sel, n_cams, cams_packed)) return st;
+    int64_t grid;
+    if (const int st = row_grid(n_rows, grid)) return st;
+    dispatch_int<kModeEuler, kModeQuat, kMode6d>(mode, [&](auto m) {
+        fuse_rotations_sym_kernel<decltype(m)::value>
+            <<<(unsigned)grid, kThreads, 0, reinterpret_cast<hipStream_t>(stream)>>>(
+                raw_dev, scene_dev, scene_base, views_dev, X_dev, RTs_dev, n_scenes, n_cams, row0, n_rows,
+                cams_packed, n_sel, syms_dev, n_syms, rounds, rot_views_dev, R_dev, pose_dev, spread_dev,
+                slot_status_dev, row_status_dev, sym_index_dev, sym_margin_dev, n_changed_dev);
+    });
+    return mvm_check_launch("fuse_rotations_sym_kernel");
 }
 
 }  // extern "C"

@@ -398,7 +398,7 @@ class MatchTable:
         return ops_views.crop_views(images, self.scene, views, self.boxes, self.n_cams, rows=rows, cams=cams,
                                     **kw)
 
-    def poses(self, raw: torch.Tensor, RTs, mode: str, rows=None, cams=None, **kw):
+    def poses(self, raw: torch.Tensor, RTs, mode: str, rows=None, cams=None, syms=None, rounds: int = 2, **kw):
         """The poses of the table's rows from a rotation head's raw outputs
         (``ops_views.fuse_rotations`` on the table's own ``scene`` / ``views``
         / ``X``): ``raw`` float32 [rows, cams, D] on the device,
@@ -409,8 +409,22 @@ class MatchTable:
         plain three-camera table, on the view table and on ``table_all()``.
         -> ``ops_views.FusedRotations``: ``pose`` f64 [rows, 4, 4] holds the
         fused rotation and the row's X (refined where the batch was), ``spread``
-        each view's distance to it."""
+        each view's distance to it.
+        With ``syms`` f64 [K, 4, 4] (the object's symmetries, as ``score``
+        takes them) the mean is taken under them, in ``rounds`` rounds
+        (``ops_views.fuse_rotations_sym``): every view is first
+        moved by the symmetry that takes it nearest the others.  That is a
+        mean: ``fuse`` is left out or "mean", and ``cam`` is a ValueError.
+        Without ``syms`` there are no rounds: ``rounds`` is not read.
+        -> ``ops_views.SymFusedRotations``."""
         views = self.views if self.views is not None else self.match
+        if syms is not None:
+            if kw.pop("fuse", "mean") != "mean":
+                raise ValueError('syms: the mean under symmetries needs fuse="mean"')
+            if "cam" in kw:
+                raise ValueError('syms: the mean under symmetries takes every view; cam= goes with fuse="cam"')
+            return ops_views.fuse_rotations_sym(raw, self.scene, views, self.X, RTs, self.n_cams, mode, syms,
+                                                rows=rows, cams=cams, rounds=rounds, **kw)
         return ops_views.fuse_rotations(raw, self.scene, views, self.X, RTs, self.n_cams, mode, rows=rows,
                                         cams=cams, **kw)
 

@@ -16,6 +16,7 @@ fake that returns None.
   mvmatch_views::fuse_rotations_out    mvm_fuse_rotations          (DESIGN §3.19)
   mvmatch_views::score_poses_out       mvm_score_poses             (DESIGN §3.20)
   mvmatch_views::match_scores_out      mvm_match_scores
+  mvmatch_views::fuse_rotations_sym_out  mvm_fuse_rotations_sym    (DESIGN §3.21)
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64, u8
 
 __all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points",
            "norm_lut", "crop_views", "fuse_rotations", "FusedRotations", "score_poses", "match_scores",
-           "recall_precision", "PoseScores"]
+           "recall_precision", "PoseScores", "fuse_rotations_sym", "SymFusedRotations"]
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # RGB
 CROP_MAX_SIZE, CROP_MAX_IMAGE = 1024, 16384
@@ -41,6 +42,8 @@ _CROP_KINDS = {torch.float32: 0, torch.float16: 1}
 ROTATION_MODES = {"euler": (0, 3), "quat": (1, 4), "6d": (2, 6)}     # name -> (code, values per slot)
 ROTATION_FUSE = {"cam": 0, "mean": 1}
 SLOT_NO_VIEW, SLOT_NO_CAPTURE, SLOT_DEGENERATE = 1, 2, 4              # FusedRotations.slot_status
+SLOT_NO_SYM = 8                                                       # SymFusedRotations.slot_status only
+SYM_MAX_ROUNDS = 4
 ROW_NO_ROTATION, ROW_AMBIGUOUS = 1, 2                                 # FusedRotations.row_status
 SYM_PADDING, SYM_NO_CAPTURE, SYM_NOT_FINITE = -1, -2, -3              # PoseScores.sym below 0
 SCORE_MAX_SYMS, SCORE_MAX_THRESHOLDS, SCORE_MAX_MATCH_GT = 64, 16, 1024
@@ -295,6 +298,56 @@ def fuse_rotations_out(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs
               ops._p(RTs), S, n_cams, row0, n_rows, (ctypes.c_int32 * len(cams))(*cams), len(cams), code,
               ROTATION_FUSE[fuse], fuse_cam, ops._p(rot_views), ops._p(R), ops._p(pose), ops._p(spread),
               ops._p(slot_status), ops._p(row_status), ops._stream(raw))
+
+
+@ops._gpu_op("fuse_rotations_sym_out", ("rot_views", "R", "pose", "spread", "slot_status", "row_status", "sym_index",
+                                        "sym_margin", "n_changed"), namespace="mvmatch_views")
+def fuse_rotations_sym_out(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs: Tensor, syms: Tensor,
+                           n_cams: int, scene_base: int, row0: int, n_rows: int, cams: List[int], mode: str,
+                           rounds: int, rot_views: Optional[Tensor], R: Tensor, pose: Tensor,
+                           spread: Optional[Tensor], slot_status: Tensor, row_status: Tensor, sym_index: Tensor,
+                           sym_margin: Optional[Tensor], n_changed: Optional[Tensor]) -> None:
+    """``fuse_rotations_out``'s mean taken under the symmetries ``syms`` f64
+    [K, 4, 4], in ``rounds`` rounds (mvm_fuse_rotations_sym).  The inputs are
+    read only; ``rot_views`` / ``spread`` / ``sym_margin`` / ``n_changed``
+    (None: not written) and the others out."""
+    dev = ops._gpu(raw, "raw", "rotation kernel")
+    if not 3 <= n_cams <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if mode not in ROTATION_MODES:
+        raise ValueError(f"mode: expected one of {sorted(ROTATION_MODES)}, got {mode!r}")
+    if not 1 <= rounds <= SYM_MAX_ROUNDS:
+        raise ValueError(f"rounds: expected 1..{SYM_MAX_ROUNDS}, got {rounds}")
+    if not 1 <= len(cams) <= n_cams or not all(0 <= c < n_cams for c in cams):
+        raise ValueError(f"cams: expected 1..{n_cams} cameras < {n_cams}, got {list(cams)}")
+    if row0 < 0 or n_rows < 0:
+        raise ValueError(f"rows: expected 0 <= begin <= end, got ({row0}, {row0 + n_rows})")
+    if RTs.dim() != 4 or tuple(RTs.shape[1:]) != (n_cams, 4, 4):
+        raise ValueError(f"RTs must be [S, {n_cams}, 4, 4], got {tuple(RTs.shape)}")
+    if syms.dim() != 3 or tuple(syms.shape[1:]) != (4, 4) or syms.shape[0] < 1:
+        raise ValueError(f"syms must be [K, 4, 4] with K >= 1, got {tuple(syms.shape)}")
+    (code, D), S, K = ROTATION_MODES[mode], int(RTs.shape[0]), int(syms.shape[0])
+    n_end, n_slots = row0 + n_rows, n_rows * len(cams)
+    rows = [(raw, "raw", f32, D * n_slots, EXACT), (scene, "scene", i32, n_end, AT_LEAST),
+            (views, "views", i32, n_cams * n_end, AT_LEAST), (X, "X", f64, 3 * n_end, AT_LEAST),
+            (RTs, "RTs", f64, 16 * n_cams * S, EXACT), (syms, "syms", f64, 16 * K, EXACT),
+            (R, "R", f64, 9 * n_rows, EXACT), (pose, "pose", f64, 16 * n_rows, EXACT),
+            (slot_status, "slot_status", i32, n_slots, EXACT), (row_status, "row_status", i32, n_rows, EXACT),
+            (sym_index, "sym_index", i32, n_slots, EXACT)]
+    for t, name, dt, size in ((rot_views, "rot_views", f64, 9 * n_slots), (spread, "spread", f64, n_slots),
+                              (sym_margin, "sym_margin", f64, n_slots), (n_changed, "n_changed", i32, n_rows)):
+        if t is not None:
+            rows.append((t, name, dt, size, EXACT))
+    ops._check_args(dev, rows)
+    if n_rows == 0:
+        return                       # no row: nothing to launch
+    if S == 0:
+        raise ValueError("RTs holds no capture")
+    ops._call("mvm_fuse_rotations_sym", ops._p(raw), D, ops._p(scene), scene_base, ops._p(views), ops._p(X),
+              ops._p(RTs), S, n_cams, row0, n_rows, (ctypes.c_int32 * len(cams))(*cams), len(cams), code,
+              ops._p(syms), K, rounds, ops._p(rot_views), ops._p(R), ops._p(pose), ops._p(spread),
+              ops._p(slot_status), ops._p(row_status), ops._p(sym_index), ops._p(sym_margin), ops._p(n_changed),
+              ops._stream(raw))
 
 
 @ops._gpu_op("score_poses_out", ("err", "sym", "t_err", "rot_cos"), namespace="mvmatch_views")
@@ -691,6 +744,70 @@ def score_poses(pose: Tensor, scene: Tensor, gt_pose, gt_offs, verts, syms=None,
     torch.ops.mvmatch_views.score_poses_out(pose.contiguous(), scene.contiguous(), gt_pose.contiguous(),
                                             offs_dev.contiguous(), verts, syms, int(scene_base), g_max, begin, m,
                                             out.err, out.sym, out.t_err, out.rot_cos)
+    return out
+
+
+@dataclass
+class SymFusedRotations(FusedRotations):
+    """What ``fuse_rotations_sym`` returns, on the device: ``FusedRotations``
+    with ``rot_views`` the aligned views ``W S_k`` of the last round, ``spread``
+    their distance to ``R``, SLOT_NO_SYM among ``slot_status``, and:"""
+    sym_index: Tensor            # int32 [n, K]          the symmetry each view took in the last round, -1 where unusable
+    sym_margin: Tensor           # float64 [n, K]        its score minus the next best (+inf: no other), NaN where unusable
+    n_changed: Tensor            # int32 [n]             views whose symmetry the last round changed (0: converged)
+
+
+def fuse_rotations_sym(raw: Tensor, scene: Tensor, views: Tensor, X: Tensor, RTs, n_cams: int, mode: str, syms,
+                       rows: Optional[Sequence[int]] = None, cams: Optional[Sequence[int]] = None,
+                       rounds: int = 2, scene_base: int = 0) -> SymFusedRotations:
+    """``fuse_rotations(fuse="mean")`` for a symmetric object (device; DESIGN
+    §3.21): a head may answer, per view, any of the rotations ``R S_k`` that
+    look alike from there, and their plain mean is none of them.  ``syms`` f64
+    [K, 4, 4], K >= 1: the object's symmetry transforms as ``score_poses``
+    takes them (a host array, checked and copied once, or a device tensor;
+    only the rotation blocks are read).  Every other argument is
+    ``fuse_rotations``'s.  Per row the first usable view in the order of
+    ``cams`` is the reference; every usable view is multiplied by the symmetry
+    that takes it nearest the reference (the lowest index of equal ones), the
+    chordal mean of the aligned views is taken, and the same is done again
+    with that mean as the reference, ``rounds`` (1..4) times in all.
+    tests/pose_sym_model.py states every step; the result is its bits, and
+    with the identity alone ``fuse="mean"``'s numbers.
+    -> ``SymFusedRotations``.  ``slot_status`` is SLOT_NO_SYM where no symmetry
+    left the view usable (a NaN, infinite or absurd ``syms``); such a view
+    leaves the mean.  ``sym_margin`` near 0 marks a view between two symmetry
+    elements; ``n_changed`` > 0 a row that another round would still move."""
+    n_cams = int(n_cams)
+    n = int(scene.shape[0])
+    if rows is None:
+        rows = (0, n)
+    try:
+        begin, end = (int(r) for r in rows)
+    except (TypeError, ValueError):
+        raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+    if not 0 <= begin <= end <= n:
+        raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+    cams = list(range(n_cams)) if cams is None else [int(c) for c in cams]
+    if mode not in ROTATION_MODES:
+        raise ValueError(f"mode: expected one of {sorted(ROTATION_MODES)}, got {mode!r}")
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= SYM_MAX_ROUNDS:
+        raise ValueError(f"rounds: expected 1..{SYM_MAX_ROUNDS}, got {rounds!r}")
+    dev = raw.device
+    m, K, D = end - begin, len(cams), ROTATION_MODES[mode][1]
+    if raw.dim() != 3 or tuple(raw.shape) != (m, K, D):
+        raise ValueError(f"raw must be [{m}, {K}, {D}] for mode {mode!r}, got {tuple(raw.shape)}")
+    if not isinstance(RTs, Tensor):
+        RTs = torch.from_numpy(np.ascontiguousarray(RTs, np.float64)).to(dev)
+    syms = _model_array(syms, "syms", (4, 4), dev)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = SymFusedRotations(R=e((m, 3, 3), f64), pose=e((m, 4, 4), f64), rot_views=e((m, K, 3, 3), f64),
+                            spread=e((m, K), f64), slot_status=e((m, K), i32), row_status=e(m, i32),
+                            sym_index=e((m, K), i32), sym_margin=e((m, K), f64), n_changed=e(m, i32))
+    torch.ops.mvmatch_views.fuse_rotations_sym_out(raw, scene.contiguous(), views.contiguous(), X.contiguous(),
+                                                   RTs.contiguous(), syms, n_cams, int(scene_base), begin, m,
+                                                   cams, mode, rounds, out.rot_views, out.R, out.pose, out.spread,
+                                                   out.slot_status, out.row_status, out.sym_index,
+                                                   out.sym_margin, out.n_changed)
     return out
 
 

@@ -58,6 +58,8 @@ extern "C" {
                            struct changed) */
 #define MVM_HAS_SCORES 1 /* mvm_score_poses, mvm_match_scores: additions to ABI 8 (no existing
                             signature or struct changed) */
+#define MVM_HAS_SYM_FUSE 1 /* mvm_fuse_rotations_sym: an addition to ABI 8 (no existing signature
+                              or struct changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -1050,6 +1052,70 @@ int mvm_match_scores(const double *err_dev, int32_t g_max, const int64_t *row_of
                      const int64_t *gt_offs_dev, int32_t n_scenes, const double *thresholds_host,
                      int32_t n_thresholds, int32_t *gt_index_dev, int32_t *tp_dev,
                      int64_t n_rows_total, mvm_stream_t stream);
+
+/*
+ * The chordal mean of a row's views under the object's symmetries (an addition
+ * to ABI 8, announced by MVM_HAS_SYM_FUSE).  A head that
+ * sees a symmetric part may answer, per view, any of the rotations R S_k that
+ * look alike from there; mvm_fuse_rotations' mean of such views is none of
+ * them.  Here every view is first multiplied by the symmetry that takes it
+ * nearest a reference, and the mean is taken of the aligned views.
+ * raw_dev .. mode are mvm_fuse_rotations' arguments and mean the same: slots,
+ * decoding, W = RTs[s][c][:3][:3]^T M and the slot statuses 1, 2 and 4.
+ *   syms_dev  f64 [n_syms, 4, 4]: the symmetry transforms as mvm_score_poses
+ *             takes them; only the top-left 3 x 3 block S_k of each is read.
+ *             Any length from 1 (a discretised continuous symmetry is long);
+ *   rounds    1..4 (2 is the usual choice).
+ * Per row, with its slots in the order of cams_host:
+ *   1. the reference R_ref is the W of the first slot of status 0; a row
+ *      without one has row status 1;
+ *   2. per slot of status 0: B = R_ref^T W, s_k = sum_ij B_ij S_k,ji (the trace
+ *      of B S_k; (i, j) row-major, left to right) for k ascending; s_k > best (from -inf) moves best to
+ *      second and takes k, else s_k > second replaces second: the lowest index
+ *      wins a tie and a NaN is never taken.  W' = W S_k.  A slot where no k was
+ *      taken, or whose W' has an entry that is not below 2^500 in magnitude,
+ *      gets slot status 8 and is not used again;
+ *   3. R = the chordal mean of the W' of the slots still of status 0, exactly
+ *      as mvm_fuse_rotations' fuse 1 takes it; a row that has lost every slot
+ *      has row status 1;
+ *   4. steps 2 and 3 again with R_ref = R, `rounds` times in all: the first
+ *      round is aligned to one view, the later ones to the mean of all.
+ * tests/pose_sym_model.py states every step; the kernel returns its bits.
+ * With the identity as the only symmetry every output shared with
+ * mvm_fuse_rotations' fuse 1 equals it as a number.  Outputs per row or slot:
+ *   rot_views_dev   f64 [n_rows, n_sel, 3, 3], may be NULL: W' of the last
+ *                   round, NaN where the slot's status is not 0;
+ *   R_dev, pose_dev, row_status_dev: as mvm_fuse_rotations writes them; row
+ *                   status 2 by the eigenvalue gap of the last mean;
+ *   spread_dev      f64 [n_rows, n_sel], may be NULL: the squared Frobenius
+ *                   distance of W' to R, NaN where the slot's status is not 0;
+ *   slot_status_dev int32 [n_rows, n_sel]: 0, 1, 2, 4 or 8;
+ *   sym_index_dev   int32 [n_rows, n_sel]: the k of the last round, -1 where
+ *                   the slot's status is not 0;
+ *   sym_margin_dev  f64 [n_rows, n_sel], may be NULL: best - second of the last
+ *                   round (+inf where one score was taken), NaN where the
+ *                   slot's status is not 0: small for a view that sits between
+ *                   two symmetry elements;
+ *   n_changed_dev   int32 [n_rows], may be NULL: the slots of status 0 whose k
+ *                   of the last round is not that of the round before (0 for
+ *                   rounds 1, 0 once converged).
+ * slot_status_dev and sym_index_dev also carry a row's state from round to
+ * round: each thread reads back what it wrote.  One launch on `stream`, a
+ * thread per row; no allocation, copy or synchronisation.  n_rows == 0 is
+ * MVM_OK whatever the other arguments are.  Refused before the launch:
+ * everything mvm_fuse_rotations refuses of the shared arguments; n_syms < 1;
+ * rounds outside 1..4; a NULL pointer other than rot_views_dev, spread_dev,
+ * sym_margin_dev and n_changed_dev.
+ */
+int mvm_fuse_rotations_sym(const float *raw_dev, int32_t D, const int32_t *scene_dev, int32_t scene_base,
+                           const int32_t *views_dev, const double *X_dev, const double *RTs_dev,
+                           int32_t n_scenes, int32_t n_cams, int64_t row0, int64_t n_rows,
+                           const int32_t *cams_host, int32_t n_sel, int32_t mode, const double *syms_dev,
+                           int32_t n_syms, int32_t rounds, double *rot_views_dev /* may be NULL */,
+                           double *R_dev, double *pose_dev, double *spread_dev /* may be NULL */,
+                           int32_t *slot_status_dev, int32_t *row_status_dev, int32_t *sym_index_dev,
+                           double *sym_margin_dev /* may be NULL */, int32_t *n_changed_dev /* may be NULL */,
+                           mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory
