@@ -238,6 +238,12 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, _vp, _vp,       # rot_views (may be NULL), R, pose, spread (may be NULL), slot_status, row_status (out)
         _vp, _vp, _vp,                      # sym_index, sym_margin (may be NULL), n_changed (may be NULL) (out)
         _vp]),                              # stream
+    "mvm_fit_boxes": (ctypes.c_int, [
+        _vp, _vp, _i32, _vp, _vp,           # pose, scene, scene_base, views, boxes
+        _i64, _i32, _vp, _i32,              # n_rows, n_cams, proj, n_scenes
+        _vp, _i32, _i32,                    # verts, n_verts, max_evals
+        _vp, _vp, _vp, _vp, _vp,            # pose_out, rms, info, cov (may be NULL), resid (may be NULL) (out)
+        _vp]),                              # stream
     "mvm_hbm_write_probe": (ctypes.c_int, [_vp, _sz, _vp]),
 }
 

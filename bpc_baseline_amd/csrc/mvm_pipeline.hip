@@ -32,6 +32,7 @@
 #include "mvmatch.h"
 #include "mvm_device.h"
 #include "mvm_internal.h"
+#include "mvm_refine.h"
 
 #pragma clang fp contract(off)
 
@@ -757,12 +758,11 @@ __global__ __launch_bounds__(kCompactThreads) void prune_views_kernel(
 // under the mask's bit, so no register array is indexed by a runtime value.
 // Every product, sum, division and square root is rounded on its own (this
 // file's fp contract(off)), in the order of tests/refine_model.py, whose bits
-// the kernel returns.
+// the kernel returns.  The 3 x 3 factorisation (refine_ldlt, refine_finite) is
+// mvm_refine.h's, shared with the box fit (mvm_boxfit.hip).
 struct RefineSums {
     double cost, A[6], g[3];     // A: A00 A01 A02 A11 A12 A22
 };
-
-__device__ __forceinline__ bool refine_finite(double x) { return __builtin_fabs(x) < INFINITY; }
 
 // cost, A and g at X over the views of `mask`, ascending
 __device__ __forceinline__ void refine_sums(const double *proj_s, uint32_t mask,
@@ -797,24 +797,6 @@ __device__ __forceinline__ void refine_sums(const double *proj_s, uint32_t mask,
             e.g[2] = e.g[2] + (a2 * ru + b2 * rv);
         }
     }
-}
-
-// M = L D L^T of the symmetric M (upper triangle, row-major) in the model's
-// order -> every pivot > 0 (a NaN is not); the factors mean nothing otherwise
-struct RefineLdlt {
-    double d0, d1, d2, l10, l20, l21;
-};
-
-__device__ __forceinline__ bool refine_ldlt(double M00, double M01, double M02, double M11,
-                                            double M12, double M22, RefineLdlt &f) {
-    f.d0 = M00;
-    f.l10 = M01 / f.d0;
-    f.l20 = M02 / f.d0;
-    f.d1 = M11 - f.l10 * M01;
-    const double t = M12 - f.l20 * M01;
-    f.l21 = t / f.d1;
-    f.d2 = (M22 - f.l20 * M02) - f.l21 * t;
-    return f.d0 > 0.0 && f.d1 > 0.0 && f.d2 > 0.0;
 }
 
 __global__ __launch_bounds__(kCompactThreads) void refine_points_kernel(

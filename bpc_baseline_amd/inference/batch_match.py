@@ -428,6 +428,31 @@ class MatchTable:
         return ops_views.fuse_rotations(raw, self.scene, views, self.X, RTs, self.n_cams, mode, rows=rows,
                                         cams=cams, **kw)
 
+    def fit_boxes(self, pose: torch.Tensor, verts, proj=None, Ks=None, RTs=None, rows=None, **kw):
+        """Each pose's translation fitted to the table's boxes, given the
+        model (``ops_views.fit_boxes`` on the table's own ``scene`` / ``views``
+        / ``boxes``): ``pose`` f64 [rows, 4, 4] on the device,
+        for example ``poses(...).pose``, whose translation is the table's X --
+        the triangulation of box centres, which are not the projections of
+        the object's origin; ``verts`` f64 [V, 3] the model's vertices as
+        ``score`` takes them; ``rows`` exactly as in ``poses``.  The rig is
+        ``proj`` f64 [S, n_cams, 3, 4] (host or device), or ``Ks`` [S, n_cams,
+        3, 3] and ``RTs`` [S, n_cams, 4, 4], from which it is built as the
+        host rig builds it (``projection_matrices``); giving both or neither
+        is a ValueError.  The other keywords are ``fit_boxes``'s
+        (``max_evals``, ``cov``, ``resid``, ``scene_base``).  Works on the
+        plain three-camera table, on the view table and on ``table_all()``.
+        -> ``ops_views.BoxFit``; its ``pose`` goes straight into
+        ``score(pose=...)``."""
+        if (proj is None) == (Ks is None and RTs is None):
+            raise ValueError("the rig: give proj, or Ks and RTs, not both and not neither")
+        if proj is None:
+            if Ks is None or RTs is None:
+                raise ValueError("the rig: Ks and RTs go together")
+            proj = projection_matrices(np.asarray(Ks), np.asarray(RTs))
+        views = self.views if self.views is not None else self.match
+        return ops_views.fit_boxes(pose, self.scene, views, self.boxes, proj, self.n_cams, verts, rows=rows, **kw)
+
     def score(self, gt_pose, gt_offs, verts=None, syms=None, pose=None, thresholds=None, rows=None,
               scene_base: int = 0):
         """The table's rows against ground truth (``ops_views.score_poses`` on

@@ -17,6 +17,7 @@ fake that returns None.
   mvmatch_views::score_poses_out       mvm_score_poses             (DESIGN §3.20)
   mvmatch_views::match_scores_out      mvm_match_scores
   mvmatch_views::fuse_rotations_sym_out  mvm_fuse_rotations_sym    (DESIGN §3.21)
+  mvmatch_views::fit_boxes_out         mvm_fit_boxes               (DESIGN §3.22)
 """
 from __future__ import annotations
 
@@ -34,7 +35,7 @@ from .ops import ANY, AT_LEAST, EXACT, f32, f64, i32, i64, u8
 
 __all__ = ["prune_views", "seed_order", "mark_used", "leftover_counts", "leftover_gather", "refine_points",
            "norm_lut", "crop_views", "fuse_rotations", "FusedRotations", "score_poses", "match_scores",
-           "recall_precision", "PoseScores", "fuse_rotations_sym", "SymFusedRotations"]
+           "recall_precision", "PoseScores", "fuse_rotations_sym", "SymFusedRotations", "fit_boxes", "BoxFit"]
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)     # RGB
 CROP_MAX_SIZE, CROP_MAX_IMAGE = 1024, 16384
@@ -418,6 +419,46 @@ def match_scores_out(err: Tensor, row_offs: Tensor, gt_offs: Tensor, thresholds:
         return                       # no row and no capture: nothing to write
     ops._call("mvm_match_scores", ops._p(err), g_max, ops._p(row_offs), ops._p(gt_offs), S,
               (ctypes.c_double * T)(*thresholds), T, ops._p(gt_index), ops._p(tp), n, ops._stream(err))
+
+
+@ops._gpu_op("fit_boxes_out", ("pose_out", "rms", "info", "cov", "resid"), namespace="mvmatch_views")
+def fit_boxes_out(pose: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, proj: Tensor, verts: Tensor,
+                  n_cams: int, scene_base: int, max_evals: int, pose_out: Tensor, rms: Tensor, info: Tensor,
+                  cov: Optional[Tensor], resid: Optional[Tensor]) -> None:
+    """Fit every row's translation to its views' boxes, given the model
+    (mvm_fit_boxes).  ``pose`` / ``scene`` / ``views`` / ``boxes`` / ``proj`` /
+    ``verts`` are read only; ``pose_out`` / ``rms`` / ``info`` and ``cov`` /
+    ``resid`` (None: not computed) out."""
+    dev = ops._gpu(pose, "pose", "box fit")
+    if not 3 <= n_cams <= _native.MVM_MAX_CAMS:
+        raise ValueError(f"n_cams: expected 3..{_native.MVM_MAX_CAMS}, got {n_cams}")
+    if pose.dim() != 3 or tuple(pose.shape[1:]) != (4, 4):
+        raise ValueError(f"pose must be [n, 4, 4], got {tuple(pose.shape)}")
+    if proj.dim() != 4 or tuple(proj.shape[1:]) != (n_cams, 3, 4):
+        raise ValueError(f"proj must be [S, {n_cams}, 3, 4], got {tuple(proj.shape)}")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError(f"verts must be [V, 3] with V >= 1, got {tuple(verts.shape)}")
+    max_evals = _check_max_evals(max_evals)
+    n, S = int(pose.shape[0]), int(proj.shape[0])
+    rows = [(pose, "pose", f64, 16 * n, EXACT), (scene, "scene", i32, n, EXACT),
+            (views, "views", i32, n_cams * n, EXACT), (boxes, "boxes", i32, 4 * n_cams * n, EXACT),
+            (proj, "proj", f64, 12 * n_cams * S, EXACT), (verts, "verts", f64, None, ANY),
+            (pose_out, "pose_out", f64, 16 * n, EXACT), (rms, "rms", f64, 2 * n, EXACT),
+            (info, "info", i32, 2 * n, EXACT)]
+    if cov is not None:
+        rows.append((cov, "cov", f64, 6 * n, EXACT))
+    if resid is not None:
+        rows.append((resid, "resid", f64, 4 * n_cams * n, EXACT))
+    ops._check_args(dev, rows)
+    if n == 0:
+        return                       # no row: nothing to launch
+    if pose_out.data_ptr() == pose.data_ptr():
+        raise ValueError("pose_out must not be pose: the input is kept")
+    if S == 0:
+        raise ValueError("proj holds no capture")
+    ops._call("mvm_fit_boxes", ops._p(pose), ops._p(scene), scene_base, ops._p(views), ops._p(boxes), n, n_cams,
+              ops._p(proj), S, ops._p(verts), int(verts.shape[0]), max_evals, ops._p(pose_out), ops._p(rms),
+              ops._p(info), ops._p(cov), ops._p(resid), ops._stream(pose))
 
 
 def mark_used(views: Tensor, match_offs: Tensor, count: Tensor, cam_offs: Tensor, used: Tensor, n_cams: int,
@@ -855,3 +896,67 @@ def recall_precision(tp: Tensor, row_offs, gt_offs):
     n_gt = as_t(gt_offs).diff().sum().to(tp.device, f64)
     hit = tp.sum(dim=1).to(f64)
     return hit / n_gt, hit / n_rows
+
+
+@dataclass
+class BoxFit:
+    """What ``fit_boxes`` returns, on the device (n rows, C cameras)."""
+    pose: Tensor                 # float64 [n, 4, 4]   the input pose with the fitted translation
+    rms: Tensor                  # float64 [n, 2]      sqrt(cost / (4 views)) at the start and at the result, pixels
+    info: Tensor                 # int32 [n, 2]        (status, evaluations): 0 converged, 1 capped, 2 failed, 3 skipped
+    cov: Optional[Tensor]        # float64 [n, 6]      the inverse normal matrix at the result (upper triangle)
+    resid: Optional[Tensor]      # float64 [n, C, 4]   (umin - x1, vmin - y1, umax - x2, vmax - y2), NaN without a view
+
+
+def fit_boxes(pose: Tensor, scene: Tensor, views: Tensor, boxes: Tensor, proj, n_cams: int, verts,
+              rows: Optional[Sequence[int]] = None, max_evals: int = 10, cov: bool = True, resid: bool = True,
+              scene_base: int = 0) -> BoxFit:
+    """Fit each pose's translation to the detected boxes, given the model
+    (device).  ``pose`` f64 [rows, 4, 4]: the rotation and the
+    start of every row of ``rows`` (for example ``FusedRotations.pose``, whose
+    translation is the table's X: the triangulation of the box centres, which
+    are not the projections of the object's origin); ``scene`` int32 [n],
+    ``views`` int32 [n, n_cams] (a three-camera table: its ``match``) and
+    ``boxes`` int32 [n, n_cams, 4] a ``MatchTable``'s fields, none written;
+    ``proj`` f64 [S, n_cams, 3, 4] (a host array, copied once, or a device
+    tensor); ``verts`` f64 [V, 3] the model's vertices as ``score_poses`` takes
+    them.  Per row, over the views with ``views >= 0`` (one is enough): the
+    summed squared distance between the edges of the detected box and of the
+    bounding box of the projected vertices is minimised over the translation
+    by ``refine_points``' damped Gauss-Newton steps, which never raise it, at
+    most ``max_evals`` (1..64) trial evaluations.  tests/box_fit_model.py
+    states every step; the result is its bits.
+    -> ``BoxFit``.  ``info[:, 0]``: 0 converged, 1 stopped at ``max_evals``, 2
+    a vertex behind a camera at the start, something not finite or a singular
+    normal matrix (the pose stands), 3 skipped: no view, or ``scene -
+    scene_base`` is no capture of ``proj`` (the pose stands; rms, cov and resid
+    NaN).  ``cov`` / ``resid`` are None with ``cov=False`` / ``resid=False``."""
+    max_evals = _check_max_evals(max_evals)       # before the op's schema turns a bool or a float into an int
+    n_cams = int(n_cams)
+    n = int(scene.shape[0])
+    if rows is None:
+        rows = (0, n)
+    try:
+        begin, end = (int(r) for r in rows)
+    except (TypeError, ValueError):
+        raise ValueError(f"rows: expected a (begin, end) pair, got {rows!r}") from None
+    if not 0 <= begin <= end <= n:
+        raise ValueError(f"rows: expected 0 <= begin <= end <= {n}, got ({begin}, {end})")
+    dev, m = pose.device, end - begin
+    if pose.dim() != 3 or tuple(pose.shape) != (m, 4, 4):
+        raise ValueError(f"pose must be [{m}, 4, 4], got {tuple(pose.shape)}")
+    if views.dim() != 2 or tuple(views.shape) != (n, n_cams):
+        raise ValueError(f"views must be [{n}, {n_cams}], got {tuple(views.shape)}")
+    if boxes.dim() != 3 or tuple(boxes.shape) != (n, n_cams, 4):
+        raise ValueError(f"boxes must be [{n}, {n_cams}, 4], got {tuple(boxes.shape)}")
+    if not isinstance(proj, Tensor):
+        proj = torch.from_numpy(np.ascontiguousarray(proj, np.float64)).to(dev)
+    verts = _model_array(verts, "verts", (3,), dev)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    out = BoxFit(pose=e((m, 4, 4), f64), rms=e((m, 2), f64), info=e((m, 2), i32),
+                 cov=e((m, 6), f64) if cov else None, resid=e((m, n_cams, 4), f64) if resid else None)
+    torch.ops.mvmatch_views.fit_boxes_out(pose.contiguous(), scene[begin:end].contiguous(),
+                                          views[begin:end].contiguous(), boxes[begin:end].contiguous(),
+                                          proj.contiguous(), verts, n_cams, int(scene_base), max_evals, out.pose,
+                                          out.rms, out.info, out.cov, out.resid)
+    return out

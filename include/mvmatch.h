@@ -60,6 +60,8 @@ extern "C" {
                             signature or struct changed) */
 #define MVM_HAS_SYM_FUSE 1 /* mvm_fuse_rotations_sym: an addition to ABI 8 (no existing signature
                               or struct changed) */
+#define MVM_HAS_BOX_FIT 1 /* mvm_fit_boxes: an addition to ABI 8 (no existing signature or struct
+                             changed) */
 #define MVM_MAX_CAMS 8
 #define MVM_MAX_PAIRS 28 /* MVM_MAX_CAMS choose 2 */
 
@@ -1116,6 +1118,62 @@ int mvm_fuse_rotations_sym(const float *raw_dev, int32_t D, const int32_t *scene
                            int32_t *slot_status_dev, int32_t *row_status_dev, int32_t *sym_index_dev,
                            double *sym_margin_dev /* may be NULL */, int32_t *n_changed_dev /* may be NULL */,
                            mvm_stream_t stream);
+
+/*
+ * The translation of a pose fitted to the detected boxes, given the model (an
+ * addition to ABI 8, announced by MVM_HAS_BOX_FIT).  The
+ * table's X is the triangulation of the views' box centres, and a box centre
+ * is not the projection of the object's origin; with the rotation known, the
+ * box extents say where the origin is.  Inputs, none written, row w of n_rows:
+ *   pose_dev  f64 [n_rows, 4, 4]: R = pose[w][:3][:3] (for example
+ *             mvm_fuse_rotations' pose_dev) and the start t0 = pose[w][:3][3];
+ *   scene_dev int32 [n_rows], scene_base: s = scene[w] - scene_base;
+ *   views_dev int32 [n_rows, n_cams] (a three-camera table passes its match
+ *             array): the kept set is K = {d < n_cams : views[w][d] >= 0},
+ *             ascending.  Only the sign is read;
+ *   boxes_dev int32 [n_rows, n_cams, 4]: (x1, y1, x2, y2) of every view;
+ *   proj_dev  f64 [n_scenes, n_cams, 3, 4], row-major;
+ *   verts_dev f64 [n_verts, 3]: the model's vertices in the object's frame.
+ * Per view of K and point t the vertices are projected, h = P[:, :3] R v +
+ * (P[:, :3] t + P[:, 3]), u = h0 / h2, v = h1 / h2, and their extremes umin,
+ * vmin, umax, vmax are taken (strict compares in ascending vertex order: the
+ * lowest vertex wins a tie), each with its vertex's depth h2.  The residuals
+ * are (umin - x1, vmin - y1, umax - x2, vmax - y2), the cost their summed
+ * squares over K, +inf where some vertex's h2 is not > 0.  An edge's row of the
+ * Jacobian is that of its extreme vertex, (P[q][j] - p P[2][j]) / h2.  From t0
+ * the cost is minimised by mvm_refine_points' damped Gauss-Newton steps and
+ * loop (lambda from 1e-3, factors of 10, floor 1e-15, a step taken only where
+ * it lowers the cost, until delta.delta <= 1e-20 t.t or max_evals (1..64) trial
+ * costs were evaluated).  Every operation and its order are stated by
+ * tests/box_fit_model.py, whose bits the kernel returns.  Outputs per row:
+ *   pose_out_dev f64 [n_rows, 4, 4]  the input pose with the fitted t (never a
+ *                higher cost than t0); R and the bottom row bit for bit;
+ *   rms_dev      f64 [n_rows, 2]     sqrt(cost / (4 |K|)) at t0 and at the
+ *                result, pixels;
+ *   info_dev     int32 [n_rows, 2]   (status, trial costs evaluated); status
+ *                0: converged, 1: stopped at max_evals, 2: a non-finite cost
+ *                (a vertex behind a camera at t0), A, g or delta, or a pivot
+ *                that is not > 0 (the result is t0, as for mvm_refine_points),
+ *                3: skipped, since s is no capture of proj_dev or K is empty
+ *                (pose_out = pose; rms, cov and resid NaN).  One view is
+ *                enough: four edges constrain three unknowns;
+ *   cov_dev      f64 [n_rows, 6]     may be NULL; the upper triangle,
+ *                row-major, of the inverse of the undamped A at the result,
+ *                NaN where a pivot is not > 0;
+ *   resid_dev    f64 [n_rows, n_cams, 4]  may be NULL; the four residuals at
+ *                the result, NaN in the views outside K.
+ * One launch on `stream`, a wave per row; no allocation, copy or
+ * synchronisation.  n_rows == 0 is MVM_OK whatever the other arguments are.
+ * Refused before the launch: a NULL pointer other than cov_dev and resid_dev,
+ * n_cams outside 3..MVM_MAX_CAMS, n_verts < 1, max_evals outside 1..64, a
+ * negative n_rows or n_scenes, and pose_out_dev overlapping pose_dev.
+ */
+int mvm_fit_boxes(const double *pose_dev, const int32_t *scene_dev, int32_t scene_base,
+                  const int32_t *views_dev, const int32_t *boxes_dev, int64_t n_rows, int32_t n_cams,
+                  const double *proj_dev, int32_t n_scenes, const double *verts_dev, int32_t n_verts,
+                  int32_t max_evals, double *pose_out_dev, double *rms_dev, int32_t *info_dev,
+                  double *cov_dev /* may be NULL */, double *resid_dev /* may be NULL */,
+                  mvm_stream_t stream);
 
 /*
  * Diagnostic: fill `bytes` (multiple of 16, 16-byte aligned) of device memory
